@@ -7,9 +7,14 @@ T=500, U=50 (BASELINE.json configs[1] / configs[2]), one process per GPU, weak s
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit + "roofline" for the
-dominant kernel (the joint vocabulary-projection MFMA GEMM, timed live with HIP events on its launch
-stream) + "cpu_baseline" (the numpy/C oracle timed on the host cores, N=1 only, bounded sample).
+Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/unit/ms_per_step + "roofline" for the
+dominant kernel (the joint vocabulary-projection MFMA GEMM, timed live with HIP events on its launch stream).
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else this file
+measures or checks after the timed region: the host issue time, the secondary forms (other loss forms, the
+graph replay, the fp32 / bf16x3 modes, train.py's host synchronisations, the step without round 6's parity
+measures) and "cpu_baseline" (the numpy/C oracle timed on the host cores, N=1 only, bounded sample) with the
+loss-error checks against it.  --dump-outputs DIR writes what the last timed step leaves its caller (loss.npy and a
+fixed, seeded sample of the updated weights) for output-for-output comparisons of two builds.
 """
 import argparse
 import json
@@ -173,6 +178,20 @@ def pmc_form(path):
         return json.load(open(path)).get("loss_form", "two-call")
     except (OSError, ValueError):
         return None
+
+
+DUMP_SAMPLE = 1 << 23       # entries of the flat weight buffer --dump-outputs writes (32 MB in float32)
+
+
+def dump_outputs(path, loss, flat):
+    """--dump-outputs: what the training step leaves its caller after the last timed step - the loss it returns, and a fixed, seeded sample
+    of the flat weight buffer its update wrote.  (The gradient buffer is not an output: the optimiser consumes it inside the step and the next
+    step zeroes it; its small vectors - LayerNorm, bias and position-table sums - are f32 atomic sums, so it also carries their order noise.)"""
+    os.makedirs(path, exist_ok=True)
+    idx = np.sort(np.random.default_rng(0).choice(flat.numel, min(flat.numel, DUMP_SAMPLE), replace=False))
+    idx = torch.from_numpy(idx).to(flat.flat.device)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(1).cpu().numpy())
+    np.save(os.path.join(path, "weight_sample.npy"), flat.flat[idx].cpu().numpy())
 
 
 def _sha16(path):
@@ -350,7 +369,14 @@ def main():
     ap.add_argument("--no-trajectory", action="store_true", help="skip loss_rel_err_trajectory (a fresh model, ten SGD steps, five fp32-mode evaluations: ~4 s)")
     ap.add_argument("--no-sync-form", action="store_true", help="skip the secondary timing of train.py's loop body with its host synchronisations "
                                                                 "(fresh .int() length tensors, float(loss) every step: train.py:53,60)")
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure the host issue time, every secondary form and the "
+                                                       "CPU baseline with its loss-error checks (the --no-* switches above still apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss and a seeded sample of the updated weights "
+                                                          "to DIR/*.npy (float32)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run times the headline only: every leg behind a --no-* switch stays off
+        args.no_sync_form = args.no_two_call = args.no_graph_form = args.no_fp32_form = args.no_cpu_baseline = args.no_trajectory = True
     if args.mode == "decode":
         return decode_mode(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -498,16 +524,20 @@ def main():
                 del step_ms[:]
             elapsed, enqueue, host_cpu, last = timed_region(step, args.steps, args.warmup, world, spread=step_ms)
         run_step = lambda: step(False, 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, flat)       # before anything below takes the model further
     # what the host itself needs to issue one step: timed on a drained device (inside the timed region the issue loop runs ahead of the GPU
     # until the HIP queue is full and then waits in the launch calls - spinning, so that wait shows up as CPU time, not as idle time)
-    issue = []
-    for _ in range(3):
+    host_issue = None
+    if args.full:
+        issue = []
+        for _ in range(3):
+            fence(world)
+            t1 = time.perf_counter()
+            run_step()
+            issue.append(time.perf_counter() - t1)
         fence(world)
-        t1 = time.perf_counter()
-        run_step()
-        issue.append(time.perf_counter() - t1)
-    fence(world)
-    host_issue = float(np.median(issue))
+        host_issue = float(np.median(issue))
     probe_ms = loss_ms = attn_ms = wgrad_ms = []
     if rank == 0 and not args.graph:                  # the probes are read after the timed region: no host sync inside it
         slots = [i % 64 for i in range(max(0, args.steps - 64), args.steps)]
@@ -728,7 +758,7 @@ def main():
             # backward thread) on a drained device - the host's own cost; well below ms_per_step = the step is GPU-bound.  Inside the timed
             # region the issue loop runs ahead until the HIP queue is full and then spins in the launch calls: host_enqueue (wall) and
             # host_cpu (process CPU time, every thread incl. the runtime's) therefore approach ms_per_step and say little by themselves.
-            "host_issue_ms_per_step": round(1e3 * host_issue, 3),
+            **({"host_issue_ms_per_step": round(1e3 * host_issue, 3)} if host_issue is not None else {}),
             "host_cpu_ms_per_step": round(1e3 * host_cpu / args.steps, 3),
             "host_blocked_ms_per_step": round(max(0.0, 1e3 * (enqueue - host_cpu) / args.steps), 3),
             "host_enqueue_ms_per_step": round(1e3 * enqueue / args.steps, 3), "model_tflops": round(flops_per_utt(cfg, T, U1) * utt_s / 1e12, 2),

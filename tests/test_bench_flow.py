@@ -87,3 +87,25 @@ def test_self_launch_command_and_exit_code(tmp_path):
                          capture_output=True, text=True, timeout=600)
     assert out.returncode != 0
     assert "no GPU visible" in (out.stderr + out.stdout) and "2-rank job exited with code" in out.stderr
+
+
+def test_dump_outputs_writes_a_fixed_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: the loss + the same seeded sample of the flat weight buffer in float32, the same entries in every run; at the real
+    sample size the files stay within 64 MB"""
+    import types
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.DUMP_SAMPLE * 4 + 1024 <= 64 << 20
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 100)
+    n = 1000
+    flat = types.SimpleNamespace(numel=n, flat=torch.arange(n, dtype=torch.float32))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), torch.tensor(2.5, requires_grad=True), flat)
+    assert sorted(os.listdir(tmp_path / "a")) == ["loss.npy", "weight_sample.npy"]
+    for f in ("loss", "weight_sample"):
+        a, b = np.load(tmp_path / "a" / (f + ".npy")), np.load(tmp_path / "b" / (f + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    w = np.load(tmp_path / "a" / "weight_sample.npy")
+    assert w.shape == (100,) and len(np.unique(w)) == 100 and np.all(np.diff(w) > 0) and w.max() < n
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [2.5]

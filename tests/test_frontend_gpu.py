@@ -30,9 +30,11 @@ def test_stacking_subsampling_padding_bit_exact(fz):
     st = U.concat_frame(dev(fz["feat"]), 3, 0)
     for s in (3, 2, 1):
         assert np.array_equal(U.subsampling(st, s).cpu().numpy(), fz["sub_%d" % s])
-    # host data belongs to the reference's own numpy code (DataLoader workers, tt/dataset.py): without the reference checkout on sys.path
-    # the call fails loudly instead of touching the GPU from what may be a forked worker
-    if not os.path.isdir("/root/reference/tt"):
+    # host data belongs to the reference's own numpy code (DataLoader workers, tt/dataset.py): without the reference's tt/utils.py on
+    # sys.path the call fails loudly instead of touching the GPU from what may be a forked worker
+    try:
+        U._reference_utils()
+    except ImportError:
         with pytest.raises(ValueError, match="reference"):
             U.concat_frame(fz["feat"], 3, 0)
     # fused: two utterances of different lengths in one launch, padded to 30 rows like Dataset.pad

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT
 for v in old new old new; do
   if [ $v = old ]; then D=$R/ab/r02; else D=$R; fi
   O=$R/gpurun_out/ab_$v; rm -rf $O; mkdir -p $O
-  (cd $D && rocprofv3 --kernel-trace --stats --output-format csv -d $O -o t -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-two-call $( [ $v = new ] && echo "--no-fp32-form --no-graph-form" ) > $O/run.log 2>&1)
+  (cd $D && rocprofv3 --kernel-trace --stats --output-format csv -d $O -o t -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-two-call $( [ $v = new ] && echo "--full --no-fp32-form --no-graph-form" ) > $O/run.log 2>&1)
   echo "== $v $(tail -1 $O/run.log | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print(d["ms_per_step"])')"
   python3 - "$O/t_kernel_stats.csv" <<'PY'
 import csv,sys

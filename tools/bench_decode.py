@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Greedy decode (tt/model.py:70-108) of the C2 model on synthetic utterances: utterances/s, frames/s, host syncs,
-through the product path only.  `python bench.py --mode decode` runs this and times the oracle's frame-by-frame loop on the host
+through the product path only.  `python bench.py --mode decode --full` runs this and times the oracle's frame-by-frame loop on the host
 beside it (token check + CPU time); the full-size token parity test is tests/test_decode_gpu.py.
 
 A random-init model emits a symbol on (nearly) every frame, the worst case for the reference's full-history label-encoder

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 TAG=$1; N=$2; shift; shift
 O=$R/gpurun_out/ks_$TAG; rm -rf $O; mkdir -p $O
-(cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d $O -o t -- python3 bench.py --no-cpu-baseline --no-sync-form "$@" > $O/run.log 2>&1)
+(cd $R && rocprofv3 --kernel-trace --stats --output-format csv -d $O -o t -- python3 bench.py --full --no-cpu-baseline --no-sync-form "$@" > $O/run.log 2>&1)
 grep '^{"metric' $O/run.log | tail -1 | python3 -c 'import sys,json; d=json.loads(sys.stdin.read()); print("ms_per_step", d["ms_per_step"], "steps", d["steps"], "warmup", d["warmup"])'
 python3 - "$O" "$N" <<'PY' | tee $R/gpurun_out/ks_$TAG.txt
 import csv,sys,glob

@@ -12,7 +12,7 @@ python3 tools/prof_summary.py $OUT/trace profiles/${TAG}_bench_kernel_stats.csv 
 python3 tools/kernel_exclusive.py $OUT/trace > profiles/${TAG}_bench_step_attribution.txt
 python3 tools/gpu_busy.py $OUT/trace >> profiles/${TAG}_bench_step_attribution.txt
 # the reference's own call sequence (model(inputs, targets) + RNNTLoss) in a trace of its own
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace2 -- python3 bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-fp32-form --no-graph-form --no-sync-form --loss-form two-call > $OUT/trace2.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace2 -- python3 bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-fp32-form --no-graph-form --no-sync-form --loss-form two-call > $OUT/trace2.log 2>&1
 python3 tools/prof_summary.py $OUT/trace2 profiles/${TAG}_bench_two_call_kernel_stats.csv "bench.py --steps 4 --warmup 2 --loss-form two-call (6 steps), C2, $TAG build $COMMIT" > /dev/null
 python3 tools/kernel_exclusive.py $OUT/trace2 > profiles/${TAG}_bench_two_call_step_attribution.txt
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-two-call --no-fp32-form --no-graph-form --no-sync-form > $OUT/fetch.log 2>&1
