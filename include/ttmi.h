@@ -157,6 +157,27 @@ int ttmi_rnnt_shift_seed(const void* workspace /* of a plain ttmi_rnnt_loss_fwd 
 int ttmi_rnnt_loss_bwd_exp(void* P, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U1,
                            int V, int blank, const void* workspace, const float* grad_out, int grad_out_stride, float scale,
                            float* srow, void* srow16, void* stream);
+
+/* ---- FastEmit latency regularisation (Yu et al., ICASSP 2021) on the three loss backwards ----------------------------------------------
+ * The _fe entry points take the arguments of ttmi_rnnt_loss_bwd / _bwd_split / _bwd_exp plus fastemit_lambda (finite, >= 0; anything else
+ * is TTMI_EINVAL with a ttmi_last_error message).  The three entry points above are the _fe ones with fastemit_lambda = 0, bit for bit.
+ * The costs (ttmi_rnnt_loss_fwd*) do not change: they stay -log P(y|x).  Per lattice cell (t, u) of utterance b, with lp = log_softmax(z),
+ * ll = log P(y|x), occ = exp(alpha + beta - ll), e_l = exp(alpha(t,u) + lp(t,u,y_{u+1}) + beta(t,u+1) - ll) for u < U_b (0 otherwise) and
+ * e_b the same for blank (beta(t+1,u); the terminal term at the last cell), g = scale * grad_out[b * grad_out_stride]:
+ *     d z[k] = g * ( softmax_k * (occ + fastemit_lambda * e_l) - [k == blank] * e_b - [k == y_{u+1}] * (1 + fastemit_lambda) * e_l )
+ * i.e. the plain gradient w.r.t. lp with its label-emission entries scaled by (1 + fastemit_lambda), chained through log_softmax (the
+ * gradient-side form of NeMo's and other transducer losses).  Every row still sums to zero.  The exp-domain form changes only its per-row
+ * factor srow (times 1 + fastemit_lambda * e_l / occ) and the blank / label entries it patches in P; its consumers are unchanged.
+ * fastemit_lambda is a by-value kernel argument: a captured graph replays the value it was captured with. */
+int ttmi_rnnt_loss_bwd_fe(const void* logits, int dtype, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                          int B, int T, int U1, int V, int blank, const void* workspace, const float* grad_out,
+                          int grad_out_stride, float scale, void* grad, long ldg, float fastemit_lambda, void* stream);
+int ttmi_rnnt_loss_bwd_split_fe(void* logits, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U1,
+                                int V, int blank, const void* workspace, const float* grad_out, int grad_out_stride, float scale,
+                                float fastemit_lambda, void* stream);
+int ttmi_rnnt_loss_bwd_exp_fe(void* P, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U1,
+                              int V, int blank, const void* workspace, const float* grad_out, int grad_out_stride, float scale,
+                              float* srow, void* srow16, float fastemit_lambda, void* stream);
 int ttmi_joint_bwd_exp(const void* P, long ldg, const float* srow, const void* srow16, const float* enc, const float* dec,
                        const float* wf, const float* wp, int B, int T, int U1, int de, int dd, int J, int V, int prec, float* ctx,
                        float* ws, float* denc, float* ddec, float* g_wf, float* g_bf, float* g_wp, float* g_bp, void* stream);

@@ -530,12 +530,21 @@ __global__ __launch_bounds__(1024) void rnnt_lattice_lds_kernel(const float* __r
 }
 
 // ------------------------------------------------------------------ gradient
+// FastEmit (Yu et al. 2021), gradient-side form: the label-emission entries of d(-ll)/d lp are scaled by (1 + fe) before the chain through
+// log_softmax, so a row's gradient is softmax (occ + fe e_label) - [blank] e_blank - [label] (1 + fe) e_label.  With c = log(occ) - lse
+// (every entry is exp(logit + c) before the patches) that is c += log(1 + fe q), q = e_label / occ = exp(beta[t,u+1] - beta[t,u] + lp_label)
+// in [0, 1], and e_label scaled by (1 + fe).  Rows with u = U_b have no label term; fe == 0 never reaches this (the callers branch on fe > 0).
+__device__ __forceinline__ void fastemit_row(float& c, float& el, float fe, float log_q) {
+    c += log1pf(fe * __expf(log_q));
+    el *= 1.f + fe;
+}
+
 template <typename TL>
 __global__ __launch_bounds__(LSE_WAVES * 64) void rnnt_grad_kernel(
     const TL* logits, long ldv, const int* __restrict__ labels, const int* __restrict__ act_lens,
     const int* __restrict__ label_lens, int B, int T, int U1, int V, int blank, int vec_ok, const float* __restrict__ lse,
     const acc_t* __restrict__ alpha_d, const acc_t* __restrict__ beta_d, const acc_t* __restrict__ ll,
-    const float* __restrict__ grad_out, int grad_out_stride, float scale, TL* grad, long ldg) {
+    const float* __restrict__ grad_out, int grad_out_stride, float scale, TL* grad, long ldg, float fe) {
     constexpr int NV = 16 / sizeof(TL);
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * LSE_WAVES + (threadIdx.x >> 6);
@@ -563,7 +572,9 @@ __global__ __launch_bounds__(LSE_WAVES * 64) void rnnt_grad_kernel(
         else if (t < Tb - 1) eb = __expf((float)(a + be[di + U1]) + lpb);       // beta[t+1,u]
         if (u < Ub) {
             yv = clampi(labels[(long)b * (U1 - 1) + u], 0, V - 1);
-            el = __expf((float)(a + be[di + U1 + 1]) + (ldf<TL>(r + yv) - l));  // beta[t,u+1]
+            const float lpy = ldf<TL>(r + yv) - l;
+            el = __expf((float)(a + be[di + U1 + 1]) + lpy);                   // beta[t,u+1]
+            if (fe > 0.f) fastemit_row(c, el, fe, (float)(be[di + U1 + 1] - be[di]) + lpy);
         }
     }
     // every lane has read r[blank], r[yv] before any lane overwrites them (in-place use)
@@ -600,7 +611,7 @@ template <int KV>
 __global__ __launch_bounds__(LSE_WAVES * 64) void rnnt_grad_split_kernel(
     float* logits, long ldv, const int* __restrict__ labels, const int* __restrict__ act_lens, const int* __restrict__ label_lens, int B, int T,
     int U1, int V, int blank, const float* __restrict__ lse, const acc_t* __restrict__ alpha_d, const acc_t* __restrict__ beta_d,
-    const acc_t* __restrict__ ll, const float* __restrict__ grad_out, int grad_out_stride, float scale) {
+    const acc_t* __restrict__ ll, const float* __restrict__ grad_out, int grad_out_stride, float scale, float fe) {
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * LSE_WAVES + (threadIdx.x >> 6);
     if (row >= (long)B * T * U1) return;
@@ -630,7 +641,9 @@ __global__ __launch_bounds__(LSE_WAVES * 64) void rnnt_grad_split_kernel(
         else if (t < Tb - 1) eb = __expf((float)(a + be[di + U1]) + lpb);
         if (u < Ub) {
             yv = clampi(labels[(long)b * (U1 - 1) + u], 0, V - 1);
-            el = __expf((float)(a + be[di + U1 + 1]) + (r[yv] - l));
+            const float lpy = r[yv] - l;
+            el = __expf((float)(a + be[di + U1 + 1]) + lpy);
+            if (fe > 0.f) fastemit_row(c, el, fe, (float)(be[di + U1 + 1] - be[di]) + lpy);
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the whole row (and r[blank], r[yv]) is in registers before any lane overwrites a byte of it
@@ -764,7 +777,8 @@ __global__ __launch_bounds__(256) void rnnt_scale_exp_kernel(
     bf16_t* __restrict__ P, long ldv, const int* __restrict__ labels, const int* __restrict__ act_lens,
     const int* __restrict__ label_lens, int B, int T, int U1, int V, int blank, const float* __restrict__ lse,
     const acc_t* __restrict__ alpha_d, const acc_t* __restrict__ beta_d, const acc_t* __restrict__ ll,
-    const float* __restrict__ grad_out, int grad_out_stride, float scale, float* __restrict__ srow, bf16_t* __restrict__ srow16) {
+    const float* __restrict__ grad_out, int grad_out_stride, float scale, float* __restrict__ srow, bf16_t* __restrict__ srow16,
+    const float* __restrict__ lpl_d, float fe) {
     const long row = (long)blockIdx.x * 256 + threadIdx.x;
     if (row >= (long)B * T * U1) return;
     const int u = (int)(row % U1);
@@ -788,6 +802,13 @@ __global__ __launch_bounds__(256) void rnnt_scale_exp_kernel(
         if (u < Ub) {
             yv = clampi(labels[(long)b * (U1 - 1) + u], 0, V - 1);
             rl = __expf((float)(be[di + U1 + 1] - bcur));
+            if (fe > 0.f) {
+                // FastEmit: s_r -> s_r (1 + fe q), q = e_label / occupancy; the patched blank / label entries keep their e_blank and (1 + fe) e_label
+                const float m = 1.f + fe * __expf((float)(be[di + U1 + 1] - bcur) + lpl_d[(long)b * diag_stride(T, U1) + di]);
+                sr *= m;
+                rb /= m;
+                rl *= (1.f + fe) / m;
+            }
         }
         const float pb = ldf<bf16_t>(r + blank);
         if (yv == blank) stf<bf16_t>(r + blank, pb * (1.f - rb - rl));
@@ -863,6 +884,7 @@ Ws carve(void* ws, int B, int T, int U1) {
 }  // namespace
 
 void ttmi_rnnt_set_lattice_version(int v) { g_lattice_version = v; }
+static bool fastemit_ok(float lambda) { return __builtin_isfinite(lambda) && lambda >= 0.f; }
 void ttmi_probe_begin(int point, hipStream_t st);      // optim.hip: HIP-event timing probes (point 1 = loss forward, 2 = loss backward)
 void ttmi_probe_end(int point, hipStream_t st);
 
@@ -909,12 +931,13 @@ int ttmi_rnnt_loss_fwd(const void* logits, int dtype, long ldv, const int* label
 
 // Backward: grad[b,t,u,v] = scale * grad_out[b*grad_out_stride] * d costs[b] / d logits, same dtype as the logits, row
 // pitch ldg (columns [V, ldg) are written as zeros).  grad may alias logits (in-place) when ldg == ldv.  Cells outside
-// [0,T_b) x [0,U_b] get exact zeros.
-int ttmi_rnnt_loss_bwd(const void* logits, int dtype, long ldv, const int* labels, const int* act_lens, const int* label_lens,
-                       int B, int T, int U1, int V, int blank, const void* workspace, const float* grad_out,
-                       int grad_out_stride, float scale, void* grad, long ldg, void* stream) {
+// [0,T_b) x [0,U_b] get exact zeros.  fastemit_lambda > 0: the FastEmit gradient (include/ttmi.h); 0 is the plain one.
+int ttmi_rnnt_loss_bwd_fe(const void* logits, int dtype, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                          int B, int T, int U1, int V, int blank, const void* workspace, const float* grad_out,
+                          int grad_out_stride, float scale, void* grad, long ldg, float fastemit_lambda, void* stream) {
     TTMI_REQUIRE(logits && (labels || U1 == 1) && act_lens && label_lens && workspace && grad_out && grad,
                  "rnnt_loss_bwd: null pointer");
+    TTMI_REQUIRE(fastemit_ok(fastemit_lambda), "rnnt_loss_bwd: fastemit_lambda %g must be finite and >= 0", (double)fastemit_lambda);
     TTMI_REQUIRE(B > 0 && T > 0 && U1 > 0 && V > 0, "rnnt_loss_bwd: bad shape");
     TTMI_REQUIRE(ldv >= V && ldg >= V && (dtype == 0 || dtype == 1), "rnnt_loss_bwd: bad pitch/dtype");
     TTMI_REQUIRE(blank >= 0 && blank < V, "rnnt_loss_bwd: blank %d outside [0,%d)", blank, V);
@@ -929,14 +952,20 @@ int ttmi_rnnt_loss_bwd(const void* logits, int dtype, long ldv, const int* label
     if (dtype == 0)
         hipLaunchKernelGGL(rnnt_grad_kernel<float>, dim3(cdiv(rows, LSE_WAVES)), dim3(LSE_WAVES * 64), 0, st,
                            static_cast<const float*>(logits), ldv, labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok,
-                           w.lse, w.alpha, w.beta, w.ll, grad_out, grad_out_stride, scale, static_cast<float*>(grad), ldg);
+                           w.lse, w.alpha, w.beta, w.ll, grad_out, grad_out_stride, scale, static_cast<float*>(grad), ldg, fastemit_lambda);
     else
         hipLaunchKernelGGL(rnnt_grad_kernel<bf16_t>, dim3(cdiv(rows, LSE_WAVES)), dim3(LSE_WAVES * 64), 0, st,
                            static_cast<const bf16_t*>(logits), ldv, labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok,
-                           w.lse, w.alpha, w.beta, w.ll, grad_out, grad_out_stride, scale, static_cast<bf16_t*>(grad), ldg);
+                           w.lse, w.alpha, w.beta, w.ll, grad_out, grad_out_stride, scale, static_cast<bf16_t*>(grad), ldg, fastemit_lambda);
     ttmi_probe_end(2, st);
     TTMI_LAUNCH_CHECK("rnnt_grad_kernel");
     return TTMI_OK;
+}
+int ttmi_rnnt_loss_bwd(const void* logits, int dtype, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                       int B, int T, int U1, int V, int blank, const void* workspace, const float* grad_out,
+                       int grad_out_stride, float scale, void* grad, long ldg, void* stream) {
+    return ttmi_rnnt_loss_bwd_fe(logits, dtype, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, workspace, grad_out, grad_out_stride,
+                                 scale, grad, ldg, 0.f, stream);
 }
 
 // bf16x3 mode: the gradient of f32 logits [rows, ldv] written over them as two bf16 planes per row, [hi | lo] with pitch 2 ldv bf16 - the operand layout of the joint's
@@ -944,9 +973,11 @@ int ttmi_rnnt_loss_bwd(const void* logits, int dtype, long ldv, const int* label
 int ttmi_rnnt_loss_bwd_split_ok(long ldv, const void* logits) {
     return ldv % 64 == 0 && ldv <= 256L * 32 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
 }
-int ttmi_rnnt_loss_bwd_split(void* logits, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U1, int V,
-                             int blank, const void* workspace, const float* grad_out, int grad_out_stride, float scale, void* stream) {
+int ttmi_rnnt_loss_bwd_split_fe(void* logits, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U1,
+                                int V, int blank, const void* workspace, const float* grad_out, int grad_out_stride, float scale,
+                                float fastemit_lambda, void* stream) {
     TTMI_REQUIRE(logits && (labels || U1 == 1) && act_lens && label_lens && workspace && grad_out, "rnnt_loss_bwd_split: null pointer");
+    TTMI_REQUIRE(fastemit_ok(fastemit_lambda), "rnnt_loss_bwd_split: fastemit_lambda %g must be finite and >= 0", (double)fastemit_lambda);
     TTMI_REQUIRE(B > 0 && T > 0 && U1 > 0 && V > 0 && ldv >= V && blank >= 0 && blank < V, "rnnt_loss_bwd_split: bad shape");
     TTMI_REQUIRE(ttmi_rnnt_loss_bwd_split_ok(ldv, logits), "rnnt_loss_bwd_split: rows must be 16-byte aligned with a pitch %% 64 == 0 of at most 8192 floats (pitch %ld)", ldv);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -955,7 +986,8 @@ int ttmi_rnnt_loss_bwd_split(void* logits, long ldv, const int* labels, const in
     const int kv = (int)cdiv(ldv / 4, 64L);
     ttmi_probe_begin(2, st);
 #define SPLIT_LAUNCH(KV) hipLaunchKernelGGL(rnnt_grad_split_kernel<KV>, dim3(cdiv(rows, LSE_WAVES)), dim3(LSE_WAVES * 64), 0, st, static_cast<float*>(logits), ldv, labels, \
-                           act_lens, label_lens, B, T, U1, V, blank, w.lse, w.alpha, w.beta, w.ll, grad_out, grad_out_stride, scale)
+                           act_lens, label_lens, B, T, U1, V, blank, w.lse, w.alpha, w.beta, w.ll, grad_out, grad_out_stride, scale, \
+                           fastemit_lambda)
     if (kv <= 8) SPLIT_LAUNCH(8);
     else if (kv <= 17) SPLIT_LAUNCH(17);
     else if (kv <= 26) SPLIT_LAUNCH(26);
@@ -964,6 +996,11 @@ int ttmi_rnnt_loss_bwd_split(void* logits, long ldv, const int* labels, const in
     ttmi_probe_end(2, st);
     TTMI_LAUNCH_CHECK("rnnt_grad_split_kernel");
     return TTMI_OK;
+}
+int ttmi_rnnt_loss_bwd_split(void* logits, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U1, int V,
+                             int blank, const void* workspace, const float* grad_out, int grad_out_stride, float scale, void* stream) {
+    return ttmi_rnnt_loss_bwd_split_fe(logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, workspace, grad_out, grad_out_stride, scale,
+                                       0.f, stream);
 }
 
 // Exp-domain forms for the fused joint + loss fast path (see rnnt_prep_exp_kernel).  P bf16 [rows, ldv] = exp(logit - shift) and
@@ -1006,11 +1043,12 @@ int ttmi_rnnt_shift_seed(const void* workspace, const int* act_lens, const int* 
     return TTMI_OK;
 }
 
-int ttmi_rnnt_loss_bwd_exp(void* P, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U1,
-                           int V, int blank, const void* workspace, const float* grad_out, int grad_out_stride, float scale,
-                           float* srow, void* srow16, void* stream) {
+int ttmi_rnnt_loss_bwd_exp_fe(void* P, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U1,
+                              int V, int blank, const void* workspace, const float* grad_out, int grad_out_stride, float scale,
+                              float* srow, void* srow16, float fastemit_lambda, void* stream) {
     TTMI_REQUIRE(P && (labels || U1 == 1) && act_lens && label_lens && workspace && grad_out && srow && srow16,
                  "rnnt_loss_bwd_exp: null pointer");
+    TTMI_REQUIRE(fastemit_ok(fastemit_lambda), "rnnt_loss_bwd_exp: fastemit_lambda %g must be finite and >= 0", (double)fastemit_lambda);
     TTMI_REQUIRE(B > 0 && T > 0 && U1 > 0 && V > 0 && ldv >= V, "rnnt_loss_bwd_exp: bad shape");
     TTMI_REQUIRE(blank >= 0 && blank < V, "rnnt_loss_bwd_exp: blank %d outside [0,%d)", blank, V);
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1019,10 +1057,16 @@ int ttmi_rnnt_loss_bwd_exp(void* P, long ldv, const int* labels, const int* act_
     ttmi_probe_begin(2, st);
     hipLaunchKernelGGL(rnnt_scale_exp_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, st, static_cast<bf16_t*>(P), ldv, labels,
                        act_lens, label_lens, B, T, U1, V, blank, w.lse, w.alpha, w.beta, w.ll, grad_out, grad_out_stride, scale,
-                       srow, static_cast<bf16_t*>(srow16));
+                       srow, static_cast<bf16_t*>(srow16), w.lpl, fastemit_lambda);
     ttmi_probe_end(2, st);
     TTMI_LAUNCH_CHECK("rnnt_scale_exp_kernel");
     return TTMI_OK;
+}
+int ttmi_rnnt_loss_bwd_exp(void* P, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U1,
+                           int V, int blank, const void* workspace, const float* grad_out, int grad_out_stride, float scale,
+                           float* srow, void* srow16, void* stream) {
+    return ttmi_rnnt_loss_bwd_exp_fe(P, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, workspace, grad_out, grad_out_stride, scale,
+                                     srow, srow16, 0.f, stream);
 }
 
 }  // extern "C"

@@ -119,8 +119,11 @@ class _JointLossFn(torch.autograd.Function):
     incoming gradient."""
 
     @staticmethod
-    def forward(ctx, enc, dec, wf, bf, wp, bp, labels, act_lens, label_lens, prec, chunk, reduction, exp_state, grad_mode=True, blank=0):
-        """exp_state: None (plain fused form) or the JointNet's _ExpShift for this device (exp-domain form)"""
+    def forward(ctx, enc, dec, wf, bf, wp, bp, labels, act_lens, label_lens, prec, chunk, reduction, exp_state, grad_mode=True, blank=0,
+                fastemit_lambda=0.0):
+        """exp_state: None (plain fused form) or the JointNet's _ExpShift for this device (exp-domain form); fastemit_lambda: the FastEmit
+        weight of the loss gradient (warprnnt_pytorch.RNNTLoss), in all three chunk forms"""
+        fe = ops.check_fastemit(fastemit_lambda)
         enc, dec = enc.contiguous(), dec.contiguous()
         params = (wf, bf, wp, bp)
         wf_, bf_, wp_, bp_ = (t.detach() for t in params)
@@ -152,7 +155,7 @@ class _JointLossFn(torch.autograd.Function):
                 P, rowsum, saved, emis = ops.joint_fwd_exp(enc[c0:c1], dec[c0:c1], wf_, bf_, wp_, bp_, prec, st.cur, lab.contiguous(), blank)
                 costs[c0:c1] = ops.rnnt_loss_fwd_exp(P, rowsum, lab, al, ll, blank, ws, st.cur, st.nxt, emis, st.flag)
                 if need:
-                    srow, srow16 = ops.rnnt_loss_bwd_exp(P, lab, al, ll, blank, ws, one, 0, scale)
+                    srow, srow16 = ops.rnnt_loss_bwd_exp(P, lab, al, ll, blank, ws, one, 0, scale, fastemit_lambda=fe)
                     ops.joint_bwd_exp(P, srow, srow16, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
                 del P, rowsum, saved, emis
                 exp_ran = True
@@ -164,10 +167,10 @@ class _JointLossFn(torch.autograd.Function):
                 seeded = True
             if need and ops.joint_loss_split_supported(logits, wf_.shape[0], prec):
                 # bf16x3: the gradient leaves the loss kernel as the two bf16 planes the joint's three-term backward multiplies (round 6: no split pass over d logits)
-                planes = ops.rnnt_loss_bwd_split(logits, lab, al, ll, blank, ws, one, 0, scale)
+                planes = ops.rnnt_loss_bwd_split(logits, lab, al, ll, blank, ws, one, 0, scale, fastemit_lambda=fe)
                 ops.joint_bwd_split(planes, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
             elif need:
-                grad = ops.rnnt_loss_bwd(logits, lab, al, ll, blank, ws, one, 0, scale, inplace=True)
+                grad = ops.rnnt_loss_bwd(logits, lab, al, ll, blank, ws, one, 0, scale, inplace=True, fastemit_lambda=fe)
                 ops.joint_bwd(grad, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
             del logits, saved
         if st is not None and (exp_ran or seeded):
@@ -200,7 +203,7 @@ class _JointLossFn(torch.autograd.Function):
                     cb()
             else:
                 rets.append(gp * gout)
-        return (denc * gout, ddec * gout, *rets, None, None, None, None, None, None, None, None, None)
+        return (denc * gout, ddec * gout, *rets, None, None, None, None, None, None, None, None, None, None)
 
 
 def deferred_logits_enabled(config, prec):
@@ -295,7 +298,7 @@ class DeferredLogits(torch.Tensor):
                 self._real = self._produce()
         return self._real
 
-    def rnnt_loss(self, labels, act_lens, label_lens, blank=0, reduction="mean"):
+    def rnnt_loss(self, labels, act_lens, label_lens, blank=0, reduction="mean", *, fastemit_lambda=0.0):
         """the loss of train.py:53 on this handle's logits without forming them (called by warprnnt_pytorch.rnnt_loss; arguments already
         certified there).  None when this case has to go through the real logits (per-utterance costs that need gradients)."""
         if self._real is not None:
@@ -315,7 +318,7 @@ class DeferredLogits(torch.Tensor):
             chunk = j.default_loss_chunk(B, T, U1, False, self._prec)
         return _JointLossFn.apply(self._enc, self._dec, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
                                   j.project_layer.bias, labels, act_lens, label_lens, self._prec, int(chunk), reduction,
-                                  j.exp_shift_state(self._enc.device) if exp else None, grad, int(blank))
+                                  j.exp_shift_state(self._enc.device) if exp else None, grad, int(blank), fastemit_lambda)
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
@@ -485,7 +488,8 @@ class Transducer(nn.Module):
             return DeferredLogits(self.joint, enc_state, dec_state, prec)
         return self.joint(enc_state, dec_state)
 
-    def loss(self, inputs, inputs_length, targets, targets_length, reduction="mean", chunk=None, check_lengths=True, exp_domain=False):
+    def loss(self, inputs, inputs_length, targets, targets_length, reduction="mean", chunk=None, check_lengths=True, exp_domain=False, *,
+             fastemit_lambda=0.0):
         """Opt-in fused form of train.py:51-53 (`logits = model(inputs, targets); loss = criterion(logits, targets.int(),
         inputs_length.int(), targets_length.int())`) that never materialises the logits (API precedent: tt_espnet/model.py:35-81 returns
         the loss from forward).  Same numbers as the two-call form: the same kernels run, one chunk of `chunk` utterances at a time
@@ -496,8 +500,11 @@ class Transducer(nn.Module):
         per-row sums, so the loss never walks the lattice's rows and its gradient is consumed in factored form (include/ttmi.h).  Same
         loss and gradients up to bf16 rounding of different intermediates (tests/test_fused_loss_gpu.py states the tolerance).  The first
         call on a module (and the first after its joint weights were replaced) runs the form above and seeds the shift on the device
-        (_ExpShift): no host synchronisation."""
+        (_ExpShift): no host synchronisation.
+
+        fastemit_lambda: FastEmit regularisation of the gradient, as in warprnnt_pytorch.RNNTLoss (the loss value is unchanged)."""
         from warprnnt_pytorch import check_lengths as certify
+        fastemit_lambda = ops.check_fastemit(fastemit_lambda)
         enc_state, dec_state = self._encode(inputs, targets)
         B, T, U1 = enc_state.shape[0], enc_state.shape[1], dec_state.shape[1]
         labels, al, ll = (t.to(device=enc_state.device, dtype=torch.int32).contiguous() for t in (targets, inputs_length, targets_length))
@@ -509,7 +516,8 @@ class Transducer(nn.Module):
         j = self.joint
         return _JointLossFn.apply(enc_state, dec_state, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
                                   j.project_layer.bias, labels, al, ll, prec, int(chunk), reduction,
-                                  j.exp_shift_state(enc_state.device) if exp_domain and prec == 1 else None, torch.is_grad_enabled())
+                                  j.exp_shift_state(enc_state.device) if exp_domain and prec == 1 else None, torch.is_grad_enabled(), 0,
+                                  fastemit_lambda)
 
     def default_loss_chunk(self, B, T, U1, exp_domain=False):
         """utterances per chunk of `loss()` (JointNet.default_loss_chunk)"""

@@ -138,7 +138,7 @@ def main(argv=None):
         se = torch.tensor([start_epoch], device=dev)
         dist.broadcast(se, 0)
         start_epoch = int(se)
-    criterion = RNNTLoss()
+    criterion = RNNTLoss(fastemit_lambda=config.training.get('fastemit_lambda', 0.0))     # FastEmit: an optional key of this driver
     for epoch in range(start_epoch, config.training.epochs):
         if train_sampler is not None:
             train_sampler.set_epoch(epoch)

@@ -4,6 +4,7 @@ torch is plumbing only (device memory, current stream).  Every function here
 launches hand-written HIP kernels; none has a PyTorch/CPU fallback.
 """
 import ctypes
+import math
 import os
 import sys
 
@@ -93,8 +94,21 @@ def rnnt_loss_fwd(logits, labels, act_lens, label_lens, blank, workspace):
     return costs
 
 
-def rnnt_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, inplace=False):
-    """inplace: the gradient overwrites the logits (same dtype and pitch; the fused joint + loss path needs them only once)"""
+def check_fastemit(fastemit_lambda):
+    """-> fastemit_lambda as a float; ValueError unless it is a finite number >= 0 (the library checks again)"""
+    try:
+        v = float(fastemit_lambda)
+    except (TypeError, ValueError):
+        raise ValueError("fastemit_lambda must be a finite float >= 0, got %r" % (fastemit_lambda,)) from None
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError("fastemit_lambda must be a finite float >= 0, got %r" % (fastemit_lambda,))
+    return v
+
+
+def rnnt_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, inplace=False, fastemit_lambda=0.0):
+    """inplace: the gradient overwrites the logits (same dtype and pitch; the fused joint + loss path needs them only once).
+    fastemit_lambda > 0: the FastEmit gradient (include/ttmi.h, ttmi_rnnt_loss_bwd_fe)"""
+    fe = check_fastemit(fastemit_lambda)
     _need_cuda(logits, labels, act_lens, label_lens, workspace, grad_out)
     B, T, U1, V = logits.shape
     ld = row_pitch(logits)
@@ -107,10 +121,10 @@ def rnnt_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_o
     else:
         buf = torch.empty(B, T, U1, ld, dtype=logits.dtype, device=logits.device)
         grad, ldg = buf[..., :V], ld
-    check(lib().ttmi_rnnt_loss_bwd(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
-                                   c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(grad_out),
-                                   c_int(grad_out_stride), c_float(scale), _p(grad), c_long(ldg), _stream()),
-          "ttmi_rnnt_loss_bwd")
+    check(lib().ttmi_rnnt_loss_bwd_fe(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
+                                      c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(grad_out),
+                                      c_int(grad_out_stride), c_float(scale), _p(grad), c_long(ldg), c_float(fe), _stream()),
+          "ttmi_rnnt_loss_bwd_fe")
     if ldg != V:
         grad._ttmi_zero_pad = ldg
     return grad
@@ -490,14 +504,16 @@ def joint_loss_split_supported(logits, J, prec):
             bool(lib().ttmi_joint_bwd_split_ok(c_int(B), c_int(T), c_int(U1), c_int(J), c_int(V), c_int(prec), c_long(ld))))
 
 
-def rnnt_loss_bwd_split(logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale):
+def rnnt_loss_bwd_split(logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, fastemit_lambda=0.0):
     """the f32 logits are REPLACED by their gradient's bf16 planes [hi | lo] per row (ttmi_rnnt_loss_bwd_split); -> the same tensor, to be handed to
     joint_bwd_split only"""
+    fe = check_fastemit(fastemit_lambda)
     _need_cuda(logits, labels, act_lens, label_lens, workspace, grad_out)
     B, T, U1, V = logits.shape
-    check(lib().ttmi_rnnt_loss_bwd_split(_p(logits), c_long(row_pitch(logits)), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U1),
-                                         c_int(V), c_int(blank), _p(workspace), _p(grad_out), c_int(grad_out_stride), c_float(scale), _stream()),
-          "ttmi_rnnt_loss_bwd_split")
+    check(lib().ttmi_rnnt_loss_bwd_split_fe(_p(logits), c_long(row_pitch(logits)), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T),
+                                            c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(grad_out), c_int(grad_out_stride), c_float(scale),
+                                            c_float(fe), _stream()),
+          "ttmi_rnnt_loss_bwd_split_fe")
     return logits
 
 
@@ -578,15 +594,16 @@ def rnnt_shift_seed(workspace, act_lens, label_lens, B, T, U1, shift_next):
           "ttmi_rnnt_shift_seed")
 
 
-def rnnt_loss_bwd_exp(P, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale):
+def rnnt_loss_bwd_exp(P, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, fastemit_lambda=0.0):
     """patches P in place -> (srow f32 [rows], srow16 bf16 [rows]): d logits = srow[r] * P[r, :]"""
+    fe = check_fastemit(fastemit_lambda)
     B, T, U1, V = P.shape
     rows = B * T * U1
     srow = torch.empty(rows, dtype=torch.float32, device=P.device)
     srow16 = torch.empty(exp_padded_rows(B, T, U1), dtype=torch.bfloat16, device=P.device)[:rows]      # (pad rows: zero-filled by ttmi_joint_bwd_exp)
-    check(lib().ttmi_rnnt_loss_bwd_exp(_p(P), c_long(row_pitch(P)), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T),
-                                       c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(grad_out), c_int(grad_out_stride),
-                                       c_float(scale), _p(srow), _p(srow16), _stream()), "ttmi_rnnt_loss_bwd_exp")
+    check(lib().ttmi_rnnt_loss_bwd_exp_fe(_p(P), c_long(row_pitch(P)), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T),
+                                          c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(grad_out), c_int(grad_out_stride),
+                                          c_float(scale), _p(srow), _p(srow16), c_float(fe), _stream()), "ttmi_rnnt_loss_bwd_exp_fe")
     return srow, srow16
 
 

@@ -466,6 +466,8 @@ class GraphedStep:
       (FusedOptimizer.hyper): `decay_lr()` / `opt.lr = ...` between replays takes effect, all three optimiser kinds replay.  Other
       hyper-parameters (momentum, betas, weight decay, clip norm, world size) are by-value kernel arguments: GraphedStep snapshots them at
       capture and RAISES at the next call if one changed (re-capture with `recapture()`);
+    * the loss's FastEmit weight (`RNNTLoss(fastemit_lambda=...)`, `Transducer.loss(..., fastemit_lambda=...)`) is a by-value kernel
+      argument as well: replays use the value the step was captured with, and a change is NOT detected - call `recapture()` after it;
     * `GradSync`'s bucketed all-reduces are launched from autograd hooks inside the captured region and become graph nodes (RCCL
       collectives are capturable; every rank must capture and replay the same sequence); with a process group initialised the capture
       runs in `thread_local` error mode so that the process group's watchdog thread may keep polling its events;

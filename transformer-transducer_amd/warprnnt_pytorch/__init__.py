@@ -8,6 +8,11 @@ Same call contract: un-normalised logits in, softmax taken
 internally, int32 labels/lengths, gradient w.r.t. the logits, 'mean' divides by
 the batch and returns shape [1].  The arithmetic runs in libttmi's HIP kernels
 (csrc/rnnt.hip); there is no CPU path here.
+
+`fastemit_lambda` (keyword-only, default 0.0) adds FastEmit latency
+regularisation (Yu et al., ICASSP 2021) as the transducer-loss libraries
+expose it: the gradient favours emitting a label over emitting blank, the
+returned cost stays -log P(y|x).  Formula: include/ttmi.h.
 """
 import os
 import weakref
@@ -79,13 +84,13 @@ def check_lengths(labels, act_lens, label_lens, B, T, U1, check_max):
 
 class _RNNTLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, acts, labels, act_lens, label_lens, blank, reduction):
+    def forward(ctx, acts, labels, act_lens, label_lens, blank, reduction, fastemit_lambda=0.0):
         B, T, U1, _ = acts.shape
         acts_c = acts if ops.row_pitch(acts) is not None else acts.contiguous()     # row-padded views are consumed in place
         ws = ops.rnnt_workspace(B, T, U1, acts.device)
         costs = ops.rnnt_loss_fwd(acts_c, labels, act_lens, label_lens, blank, ws)
         ctx.save_for_backward(acts_c, labels, act_lens, label_lens, ws)
-        ctx.blank, ctx.reduction = blank, reduction
+        ctx.blank, ctx.reduction, ctx.fastemit_lambda = blank, reduction, fastemit_lambda
         if reduction == "none":
             return costs
         out = costs.sum().reshape(1)
@@ -98,11 +103,13 @@ class _RNNTLossFn(torch.autograd.Function):
         go = grad_out.contiguous().float()
         per_utt = ctx.reduction == "none"
         scale = 1.0 / B if ctx.reduction == "mean" else 1.0
-        grad = ops.rnnt_loss_bwd(acts, labels, act_lens, label_lens, ctx.blank, ws, go, 1 if per_utt else 0, scale)
-        return grad, None, None, None, None, None
+        grad = ops.rnnt_loss_bwd(acts, labels, act_lens, label_lens, ctx.blank, ws, go, 1 if per_utt else 0, scale,
+                                 fastemit_lambda=ctx.fastemit_lambda)
+        return grad, None, None, None, None, None, None
 
 
-def rnnt_loss(acts, labels, act_lens, label_lens, blank=0, reduction="mean", check_lengths=None):
+def rnnt_loss(acts, labels, act_lens, label_lens, blank=0, reduction="mean", check_lengths=None, *, fastemit_lambda=0.0):
+    fastemit_lambda = ops.check_fastemit(fastemit_lambda)
     if check_lengths is None:
         check_lengths = os.environ.get("TTMI_CHECK_LENGTHS", "1") != "0"
     if not acts.is_cuda:
@@ -113,21 +120,27 @@ def rnnt_loss(acts, labels, act_lens, label_lens, blank=0, reduction="mean", che
     if fused is not None:
         # `acts` is the handle Transducer.forward returns in the bf16 pipeline (tt.model.DeferredLogits): joint + loss run as one fused op on
         # the encoder states it carries and the logits are never formed - train.py:51-53 as written, on the path of Transducer.loss
-        out = fused(labels, act_lens, label_lens, int(blank), reduction)
+        out = fused(labels, act_lens, label_lens, int(blank), reduction, fastemit_lambda=fastemit_lambda)
         if out is not None:
             return out
         acts = acts.materialize()           # (per-utterance costs with gradients, or a handle that was already used as a tensor)
-    return _RNNTLossFn.apply(acts, labels, act_lens, label_lens, int(blank), reduction)
+    return _RNNTLossFn.apply(acts, labels, act_lens, label_lens, int(blank), reduction, fastemit_lambda)
 
 
 class RNNTLoss(torch.nn.Module):
-    """RNNTLoss(blank=0, reduction='mean')(acts, labels, act_lens, label_lens)"""
+    """RNNTLoss(blank=0, reduction='mean', *, fastemit_lambda=0.0)(acts, labels, act_lens, label_lens)
 
-    def __init__(self, blank=0, reduction="mean", check_lengths=None):
+    fastemit_lambda: FastEmit regularisation weight (finite, >= 0; 0 is the plain loss, bit for bit).  It changes the gradient only.
+    It reaches the kernels as a by-value argument, so a captured step (ttmi.train.GraphedStep) replays the value it was captured with:
+    changing it means recapturing."""
+
+    def __init__(self, blank=0, reduction="mean", check_lengths=None, *, fastemit_lambda=0.0):
         super().__init__()
         if reduction not in ("mean", "sum", "none"):
             raise ValueError("reduction must be 'mean', 'sum' or 'none'")
         self.blank, self.reduction, self.check_lengths = blank, reduction, check_lengths
+        self.fastemit_lambda = ops.check_fastemit(fastemit_lambda)
 
     def forward(self, acts, labels, act_lens, label_lens):
-        return rnnt_loss(acts, labels, act_lens, label_lens, self.blank, self.reduction, self.check_lengths)
+        return rnnt_loss(acts, labels, act_lens, label_lens, self.blank, self.reduction, self.check_lengths,
+                         fastemit_lambda=self.fastemit_lambda)
