@@ -182,6 +182,28 @@ int ttmi_joint_bwd_exp(const void* P, long ldg, const float* srow, const void* s
                        const float* wf, const float* wp, int B, int T, int U1, int de, int dd, int J, int V, int prec, float* ctx,
                        float* ws, float* denc, float* ddec, float* g_wf, float* g_bf, float* g_wp, float* g_bp, void* stream);
 
+/* ---- forced alignment and emission-time statistics (no reference counterpart: the reference's warprnnt_pytorch returns costs only) ------
+ * Both read the workspace a finished ttmi_rnnt_loss_fwd OR ttmi_rnnt_loss_fwd_exp left on the same (B, T, U1) (either forward fills the
+ * blank / label log-probs lpb / lpl, alpha, beta and ll).  The loss workspace is READ-ONLY here: a backward issued after an align / emit_stats
+ * call gives the same bits as one issued straight after the forward.  Lengths are clamped as in the loss (T_b to [1, T], U_b to [0, U1-1]).
+ * ttmi_rnnt_align: the best path.  v(0,0) = 0, v(t,u) = max(v(t-1,u) + lpb(t-1,u), v(t,u-1) + lpl(t,u-1)) for 0 <= t < T_b, 0 <= u <= U_b;
+ * score[b] (f32) = v(T_b-1, U_b) + lpb(T_b-1, U_b), the log-probability of that path.  TIE RULE: the label move is taken only when it is
+ * strictly greater; a tie goes to blank.  frames i32 [B, U1-1]: frames[b][u] = the frame t at which label u+1 is emitted (the path's move
+ * (t, u) -> (t, u+1)), non-decreasing in u, -1 for u >= U_b.  The frontier is carried in fp64 like alpha / beta.  One decision bit per cell:
+ * kept in LDS when an utterance's (T + U1 - 1) * ceil(U1 / 64) 8-byte words fit (128 KB), otherwise in align_workspace
+ * (ttmi_rnnt_align_workspace_bytes(B, T, U1) bytes, 8-byte aligned, always required, contents undefined afterwards).
+ * ttmi_set_option(23, bits) - measurements / tests only: 1 = decision words in align_workspace whatever the shape, 2 = no backtrace.
+ * ttmi_rnnt_emit_stats: e(t,u) = exp(alpha(t,u) + lpl(t,u) + beta(t,u+1) - ll) for u < U_b is the posterior probability that label u+1 is
+ * emitted at frame t; mass f32 [B, U1-1] = sum_t e(t,u) (1 for a healthy lattice: every alignment emits every label once), expected f32
+ * [B, U1-1] = sum_t t e(t,u), the expected emission frame.  Entries u >= U_b: mass 0, expected -1.
+ * Neither call synchronises with the host or issues a memset; both may be captured in a HIP graph.  U1 <= 1024 as for the loss. */
+size_t ttmi_rnnt_align_workspace_bytes(int B, int T, int U1);
+int ttmi_rnnt_align(const void* workspace /* filled by ttmi_rnnt_loss_fwd or _fwd_exp on the same (B,T,U1) */,
+                    const int* act_lens, const int* label_lens, int B, int T, int U1,
+                    void* align_workspace, int* frames, float* score, void* stream);
+int ttmi_rnnt_emit_stats(const void* workspace, const int* act_lens, const int* label_lens, int B, int T, int U1,
+                         float* expected, float* mass, void* stream);
+
 /* ---- grouped weight gradients (data-parallel hot path): the four weight-gradient GEMMs of an encoder layer are a quarter
  * of the chip each step; deferred and launched four layers at a time they are 256 tiles, one per CU over the whole reduction - no split along
  * K, no atomics, bit-identical from run to run and across ranks.  ttmi_attn_bwd_defer / ttmi_ffn_bwd_defer are ttmi_attn_bwd / ttmi_ffn_bwd
@@ -370,7 +392,8 @@ int ttmi_stream_reserve_cus(void* stream, int n);
  * 20: 0 = grouped weight gradients never cut an XCD's surplus tiles into K-pieces (default 1: under a CU reservation - ttmi_stream_reserve_cus - 256 tiles on 224 ... 248
  * workgroups end with one atomically added piece per workgroup instead of a second round; without a reservation the launches stay free of atomics either way);
  * 21: 0 = the joint's sums over frames (dPD) by f32 atomics as in rounds 1 - 5 (default 1: partial rows + an ordered second pass - the same bits in every run, same time);
- * 22: 0 = bf16x3 weight gradients as three accumulating launches (round 5) instead of one launch over the plane pairs + a fold */
+ * 22: 0 = bf16x3 weight gradients as three accumulating launches (round 5) instead of one launch over the plane pairs + a fold;
+ * 23: ttmi_rnnt_align bits: 1 = decision words in the caller's workspace whatever the shape, 2 = forward walk only, no backtrace (frames of real labels are not written) */
 int ttmi_set_option(int key, int value);
 int ttmi_dropout_apply(const float* in, long n, float p, unsigned seed, float* out, void* stream);
 int ttmi_probe_arm(int slot);

@@ -1,5 +1,7 @@
 """alpha / beta lattice alone: ttmi_rnnt_loss_fwd on logits with a tiny vocabulary, so that the
-log-sum-exp pass is negligible and the launch is the T + U dependent diagonals.  Times both kernels (ttmi_set_option(9, v)):
+log-sum-exp pass is negligible and the launch is the T + U dependent diagonals.  Times both kernels (ttmi_set_option(9, v)), and, on the
+workspace that forward left, ttmi_rnnt_align (decision words where the shape puts them, forced into global memory, and without its
+backtrace: ttmi_set_option(23, bits)) and ttmi_rnnt_emit_stats under the same protocol:
 
     python tools/bench_lattice.py            # C2 (B=32, T=500, U=50), C5 chunk (B=4, T=2000, U=200), C5 batch (B=8)
 """
@@ -34,11 +36,32 @@ def run(B, T, U, reps=20, V=8):
         torch.cuda.synchronize()
         out[name] = (e0.elapsed_time(e1) / reps, c.clone())
     ops.set_option(9, 0)
+
+    def timed(fn):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+
+    align = {}
+    for bits, name in ((0, "default"), (1, "global words"), (2, "no backtrace")):
+        ops.set_option(23, bits)
+        align[name] = timed(lambda: ops.rnnt_align(ws, tl, ul, B, T, U + 1))
+    ops.set_option(23, 0)
+    t_stats = timed(lambda: ops.rnnt_emit_stats(ws, tl, ul, B, T, U + 1))
     (t_old, c_old), (t_new, c_new) = out["one wave per utterance"], out["workgroup + LDS frontier"]
     same = bool(torch.equal(c_old, c_new))
     D = T + U
     print("B=%d T=%d U=%d: one-wave kernel %.3f ms (%.2f us per diagonal), LDS-frontier kernel %.3f ms (%.2f us per diagonal), costs bit-identical: %s"
           % (B, T, U, t_old, 1e3 * t_old / D, t_new, 1e3 * t_new / D, same))
+    print("    ttmi_rnnt_align %.3f ms (%.2f us per diagonal; decision words in global memory %.3f ms; without the backtrace %.3f ms), "
+          "ttmi_rnnt_emit_stats %.3f ms" % (align["default"], 1e3 * align["default"] / D, align["global words"], align["no backtrace"], t_stats))
 
 
 if __name__ == "__main__":

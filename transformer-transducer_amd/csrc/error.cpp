@@ -12,4 +12,4 @@ void ttmi_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* ttmi_last_error(void) { return g_err; }
-extern "C" int ttmi_version(void) { return 100; }
+extern "C" int ttmi_version(void) { return 101; }

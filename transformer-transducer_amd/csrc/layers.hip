@@ -20,6 +20,7 @@
 void ttmi_probe_begin(int slot, hipStream_t st);
 void ttmi_probe_end(int slot, hipStream_t st);
 void ttmi_rnnt_set_lattice_version(int v);      // rnnt.hip
+void ttmi_rnnt_set_align_debug(int v);          // rnnt.hip
 
 namespace {
 
@@ -1604,11 +1605,12 @@ int ttmi_set_dropout_salt(const unsigned* salt) {
 // process-wide switches for A/B measurements.  key 0: 1 = disable the fused attention kernels (bf16 pipeline only);
 // key 1: throughput-GEMM generation (see gemm_fast.hip); key 2: flash-kernel timing switches; key 3: 0 = no wgrad fork
 int ttmi_set_option(int key, int value) {
-    TTMI_REQUIRE(key >= 0 && key <= 22, "set_option: unknown key %d", key);
+    TTMI_REQUIRE(key >= 0 && key <= 23, "set_option: unknown key %d", key);
     if (key == 19) { g_joint_dec_lo = value; return TTMI_OK; }
     if (key == 20) { gemm_fast_set_tn_group_pieces(value); return TTMI_OK; }
     if (key == 21) { g_joint_dpd_two_pass = value; return TTMI_OK; }
     if (key == 22) { g_x3_tn_one_launch = value; return TTMI_OK; }
+    if (key == 23) { ttmi_rnnt_set_align_debug(value); return TTMI_OK; }
     if (key == 18) { g_capture_forks = value; return TTMI_OK; }
     if (key == 17) { gemm_fast_set_f32(value); return TTMI_OK; }
     if (key == 16) { g_scatter_launch = value; return TTMI_OK; }

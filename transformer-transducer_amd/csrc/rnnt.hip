@@ -17,6 +17,9 @@
 //                          chunks ahead.  No MFMA: it is not a contraction.
 //   rnnt_grad_kernel       HBM-bound: one wave per row, reads the logits once
 //                          and writes the gradient once (in place allowed).
+//   rnnt_viterbi_kernel    forced alignment: the alpha walk with max, one decision
+//                          bit per cell, backtrace in the same kernel.
+//   rnnt_emit_stats_kernel expected emission frame of every label from alpha / beta.
 #include "common.h"
 
 namespace {
@@ -489,6 +492,12 @@ __global__ __launch_bounds__(1024) void rnnt_lattice_lds_kernel(const float* __r
     const int u = wave * 64 + lane;
     acc_t a = (acc_t)NEG;                        // this lane's frontier cell
     if (!helper) {
+        // LDS keeps what the previous kernel on this CU left in it.  A ring slot is accepted by its tag alone, and an earlier lattice launch of the
+        // same U1 with a SHORT utterance (T_b + U_b < 64) leaves exactly the small tags the first steps of this launch wait for: a consumer that
+        // read such a slot before its producer had written it took the old launch's cell (seen as a rare wrong beta near a wave boundary, by the
+        // emission-mass check of rnnt_emit_stats_kernel; alpha's early boundary cells lie outside the lattice).  Every slot but the initial one
+        // starts with a tag no step waits for.
+        if (lane != LAT_NB - 1) lat_slot_write(bnd + wave * LAT_NB + lane, (acc_t)NEG, -1);
         if (!do_beta) {
             a = (u == 0) ? 0.0 : (acc_t)NEG;
             if (u == 0) out[0] = 0.0;
@@ -821,6 +830,187 @@ __global__ __launch_bounds__(256) void rnnt_scale_exp_kernel(
     stf<bf16_t>(srow16 + row, sr);
 }
 
+// ------------------------------------------------------------------ forced alignment: best path through the lattice
+// v(0,0) = 0, v(t,u) = max(v(t-1,u) + lpb(t-1,u), v(t,u-1) + lpl(t,u-1)); the label move is taken only when it is STRICTLY greater (a tie goes
+// to blank).  It is the alpha walk of rnnt_alphabeta_kernel with max in place of lae, in the same shape: one wave per utterance, lane l / slot r
+// owns label u = 64 r + l, the frontier in fp64 registers, the neighbour by a one-lane DPP rotate, emission rows prefetched two chunks ahead.
+// The prefetch loads are unconditional loads of a clamped index (a guarded load inside the unrolled chunk is waited for one by one); what they
+// bring from outside the ragged lattice is uninitialised and is dropped by selects, never by arithmetic.
+// The decision of a cell is one bit (1 = reached by the label move); per diagonal and slot that is one __ballot word, stored by lane 0 at
+// dec[d * W + r] - in LDS when the utterance's words fit, else in the caller's workspace.  The backtrace follows in the same kernel: both moves
+// step one diagonal down, so the path crosses the diagonals D - 1 ... 1 in order, one cell each; the wave fetches the words of 64 diagonals at a
+// time (lane j: diagonal d - j, slot u / 64) and walks them by lane reads with t and u in scalar registers - a new fetch only after 64 steps or
+// when u leaves the slot.  Cells (0, u > 0) always carry the bit and cells (t, 0) never do, so the walk ends at (0, 0) whatever the data.
+typedef unsigned long long dec_t;
+
+template <int R, int PF>
+__device__ __forceinline__ void vit_load_rows(RowBuf<R, PF>& buf, const float* lpb, const float* lpl, int base, int D, int U1, int lane) {
+#pragma unroll
+    for (int s = 0; s < PF; ++s) {
+        int row = base + s - 1;
+        row = row < D - 1 ? row : D - 1;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int u = r * 64 + lane;
+            const int uc = u < U1 ? u : U1 - 1;
+            buf.pb[s][r] = lpb[(long)row * U1 + uc];
+            buf.pl[s][r] = lpl[(long)row * U1 + (uc > 0 ? uc - 1 : 0)];
+        }
+    }
+}
+
+template <int R, int PF, bool LDS_DEC>
+__device__ __forceinline__ void vit_steps(acc_t (&a)[R], const RowBuf<R, PF>& buf, int base, int D, int Tb, int Ub, int W, int lane,
+                                          dec_t* __restrict__ dec_l, dec_t* __restrict__ dec_g) {
+#pragma unroll
+    for (int s = 0; s < PF; ++s) {
+        const int d = base + s;
+        if (d < D) {   // wave-uniform
+            acc_t left[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                acc_t nb = rot_r1(a[r]);
+                acc_t wrap = (r > 0) ? rot_r1(a[r > 0 ? r - 1 : 0]) : (acc_t)NEG;
+                left[r] = (lane == 0) ? wrap : nb;
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int u = r * 64 + lane;
+                const int t = d - u;
+                const bool valid = (u <= Ub) && (t >= 0) && (t < Tb);
+                const acc_t tt = (t > 0) ? a[r] + (acc_t)buf.pb[s][r] : (acc_t)NEG;
+                const acc_t tu = (u > 0) ? left[r] + (acc_t)buf.pl[s][r] : (acc_t)NEG;
+                const bool lab = valid && (u > 0) && (t == 0 || tu > tt);      // strictly greater: a tie goes to blank
+                a[r] = valid ? (lab ? tu : tt) : (acc_t)NEG;
+                const dec_t w = __ballot(lab);
+                if (r < W && lane == 0) {
+                    if constexpr (LDS_DEC) dec_l[d * W + r] = w;
+                    else dec_g[(long)d * W + r] = w;
+                }
+            }
+        }
+    }
+}
+
+template <int R, int PF, bool LDS_DEC>
+__global__ __launch_bounds__(64) void rnnt_viterbi_kernel(const float* __restrict__ lpb_d, const float* __restrict__ lpl_d,
+                                                          const int* __restrict__ act_lens, const int* __restrict__ label_lens, int T, int U1,
+                                                          int W, dec_t* __restrict__ dec_ws, int* __restrict__ frames,
+                                                          float* __restrict__ score, int backtrace) {
+    extern __shared__ __attribute__((aligned(16))) char vit_smem[];
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U1 - 1);
+    const int D = Tb + Ub;   // diagonals 0 .. D-1
+    const long off = (long)b * diag_stride(T, U1);
+    const float* lpb = lpb_d + off;
+    const float* lpl = lpl_d + off;
+    dec_t* dec_l = reinterpret_cast<dec_t*>(vit_smem);                      // [D][W] (LDS_DEC)
+    dec_t* dec_g = dec_ws + (long)b * (T + U1 - 1) * W;                     // [T + U1 - 1][W] per utterance (otherwise)
+    int* fr = frames + (long)b * (U1 - 1);
+    for (int u = Ub + lane; u < U1 - 1; u += 64) fr[u] = -1;                // labels the utterance does not have
+    RowBuf<R, PF> A, Bq;
+    acc_t a[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) a[r] = (r == 0 && lane == 0) ? 0.0 : (acc_t)NEG;
+    vit_load_rows<R, PF>(A, lpb, lpl, 1, D, U1, lane);
+    for (int base = 1; base < D; base += 2 * PF) {
+        vit_load_rows<R, PF>(Bq, lpb, lpl, base + PF, D, U1, lane);
+        vit_steps<R, PF, LDS_DEC>(a, A, base, D, Tb, Ub, W, lane, dec_l, dec_g);
+        vit_load_rows<R, PF>(A, lpb, lpl, base + 2 * PF, D, U1, lane);
+        vit_steps<R, PF, LDS_DEC>(a, Bq, base + PF, D, Tb, Ub, W, lane, dec_l, dec_g);
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (r * 64 + lane == Ub) score[b] = (float)(a[r] + (acc_t)lpb[(long)(D - 1) * U1 + Ub]);
+    if (!backtrace) return;          // measurement only (ttmi_set_option(23, 2)): the forward walk alone
+    if constexpr (!LDS_DEC) __threadfence();
+    __syncthreads();                 // lane 0's decision words are visible to the whole wave
+    int t = Tb - 1, u = Ub, d = D - 1;
+    while (d > 0) {
+        const int g = u >> 6;
+        const int dl = d - lane;
+        dec_t w = 0;
+        if (dl > 0) {
+            if constexpr (LDS_DEC) w = dec_l[dl * W + g];
+            else w = dec_g[(long)dl * W + g];
+        }
+        const int wlo = (int)(unsigned)(w & 0xffffffffULL), whi = (int)(unsigned)(w >> 32);
+        for (int j = 0; j < 64 && d > 0 && (u >> 6) == g; ++j, --d) {
+            const unsigned lo = (unsigned)__builtin_amdgcn_readlane(wlo, j), hi = (unsigned)__builtin_amdgcn_readlane(whi, j);
+            const unsigned bit = (((u & 32) ? hi : lo) >> (u & 31)) & 1u;
+            if (bit && u > 0) {      // cell (t, u) was reached from (t, u - 1): label u is emitted at frame t
+                if (lane == 0) fr[u - 1] = t;
+                --u;
+            } else if (t > 0) {
+                --t;
+            }
+        }
+    }
+}
+
+// Per label, the posterior over its emission frame from a finished forward: e(t,u) = exp(alpha(t,u) + lpl(t,u) + beta(t,u+1) - ll), u < U_b.
+// mass = sum_t e (every alignment emits every label exactly once: 1, a health check of the lattice), expected = sum_t t e.  One wave per (b, u),
+// lanes stride t; reads each alpha / beta cell it needs once.  Entries u >= U_b: mass 0, expected -1.
+__global__ __launch_bounds__(256) void rnnt_emit_stats_kernel(const acc_t* __restrict__ alpha_d, const acc_t* __restrict__ beta_d,
+                                                              const acc_t* __restrict__ ll, const float* __restrict__ lpl_d,
+                                                              const int* __restrict__ act_lens, const int* __restrict__ label_lens, int B,
+                                                              int T, int U1, float* __restrict__ expected, float* __restrict__ mass) {
+    const int lane = threadIdx.x & 63;
+    const long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (w >= (long)B * (U1 - 1)) return;      // wave-uniform
+    const int u = (int)(w % (U1 - 1));
+    const int b = (int)(w / (U1 - 1));
+    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U1 - 1);
+    float m = 0.f, e1 = 0.f;
+    if (u < Ub) {
+        const long off = (long)b * diag_stride(T, U1);
+        const acc_t* al = alpha_d + off;
+        const acc_t* be = beta_d + off;
+        const float* pl = lpl_d + off;
+        const acc_t l = ll[b * 2];
+        for (int t = lane; t < Tb; t += 64) {
+            const long di = (long)(t + u) * U1 + u;
+            const float e = __expf((float)(al[di] + (acc_t)pl[di] + be[di + U1 + 1] - l));      // beta[t, u+1]
+            m += e;
+            e1 += (float)t * e;
+        }
+    }
+    m = wave_sum(m);
+    e1 = wave_sum(e1);
+    if (lane == 0) {
+        mass[w] = u < Ub ? m : 0.f;
+        expected[w] = u < Ub ? e1 : -1.f;
+    }
+}
+
+int g_align_debug = 0;          // ttmi_set_option(23, bits): 1 = decision words in the caller's workspace whatever the shape, 2 = no backtrace (measurements / tests)
+constexpr size_t VIT_LDS_MAX = 128 * 1024;      // decision words of one utterance kept in LDS up to here (of the CU's 160 KB)
+__host__ __device__ __forceinline__ size_t vit_dec_bytes(int T, int U1) { return (size_t)(T + U1 - 1) * ((U1 + 63) / 64) * sizeof(dec_t); }
+
+template <int R, int PF>
+int launch_viterbi(hipStream_t st, int B, const float* lpb, const float* lpl, const int* al, const int* ll_, int T, int U1, dec_t* dec_ws,
+                   int* frames, float* score) {
+    const int W = (U1 + 63) / 64;
+    const size_t lds = vit_dec_bytes(T, U1);
+    const int backtrace = (g_align_debug & 2) ? 0 : 1;
+    if (lds <= VIT_LDS_MAX && !(g_align_debug & 1)) {
+        if (lds > 64 * 1024) {
+            // above the default limit the attribute is needed, and it belongs to the current DEVICE: it is set on every such call (a host-side
+            // call, no stream work) instead of being remembered per process
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rnnt_viterbi_kernel<R, PF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)VIT_LDS_MAX);
+            if (e != hipSuccess) {
+                ttmi_set_error("rnnt align: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
+                return (int)e;
+            }
+        }
+        hipLaunchKernelGGL((rnnt_viterbi_kernel<R, PF, true>), dim3(B), dim3(64), lds, st, lpb, lpl, al, ll_, T, U1, W, dec_ws, frames, score, backtrace);
+    } else {
+        hipLaunchKernelGGL((rnnt_viterbi_kernel<R, PF, false>), dim3(B), dim3(64), 0, st, lpb, lpl, al, ll_, T, U1, W, dec_ws, frames, score, backtrace);
+    }
+    return TTMI_OK;
+}
+
 template <int R, int PF>
 void launch_alphabeta(hipStream_t st, int B, const float* lpb, const float* lpl, const int* al, const int* ll_, int T, int U1,
                       acc_t* a, acc_t* b, acc_t* ll, float* costs) {
@@ -884,6 +1074,7 @@ Ws carve(void* ws, int B, int T, int U1) {
 }  // namespace
 
 void ttmi_rnnt_set_lattice_version(int v) { g_lattice_version = v; }
+void ttmi_rnnt_set_align_debug(int v) { g_align_debug = v; }
 static bool fastemit_ok(float lambda) { return __builtin_isfinite(lambda) && lambda >= 0.f; }
 void ttmi_probe_begin(int point, hipStream_t st);      // optim.hip: HIP-event timing probes (point 1 = loss forward, 2 = loss backward)
 void ttmi_probe_end(int point, hipStream_t st);
@@ -1040,6 +1231,49 @@ int ttmi_rnnt_shift_seed(const void* workspace, const int* act_lens, const int* 
     hipLaunchKernelGGL(rnnt_shift_seed_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w.lse, act_lens,
                        label_lens, B, T, U1, shift_next);
     TTMI_LAUNCH_CHECK("rnnt_shift_seed_kernel");
+    return TTMI_OK;
+}
+
+// Forced alignment and emission statistics from the workspace a finished ttmi_rnnt_loss_fwd / _fwd_exp left on the same (B, T, U1); the loss
+// workspace is only read (include/ttmi.h).  No host synchronisation, no memset node: both are capturable in a HIP graph.
+size_t ttmi_rnnt_align_workspace_bytes(int B, int T, int U1) {
+    if (B <= 0 || T <= 0 || U1 <= 0) return 0;
+    return (size_t)B * vit_dec_bytes(T, U1);
+}
+
+int ttmi_rnnt_align(const void* workspace, const int* act_lens, const int* label_lens, int B, int T, int U1, void* align_workspace,
+                    int* frames, float* score, void* stream) {
+    TTMI_REQUIRE(workspace && act_lens && label_lens && align_workspace && (frames || U1 == 1) && score, "rnnt_align: null pointer");
+    TTMI_REQUIRE(B > 0 && T > 0 && U1 > 0, "rnnt_align: bad shape B=%d T=%d U1=%d", B, T, U1);
+    TTMI_REQUIRE(U1 <= 1024, "rnnt_align: U+1=%d > 1024 unsupported", U1);
+    TTMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && (reinterpret_cast<uintptr_t>(align_workspace) & 7) == 0,
+                 "rnnt_align: workspaces must be 8-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    Ws w = carve(const_cast<void*>(workspace), B, T, U1);
+    dec_t* dec = static_cast<dec_t*>(align_workspace);
+    int rc;
+    if (U1 <= 64) rc = launch_viterbi<1, 8>(st, B, w.lpb, w.lpl, act_lens, label_lens, T, U1, dec, frames, score);
+    else if (U1 <= 128) rc = launch_viterbi<2, 8>(st, B, w.lpb, w.lpl, act_lens, label_lens, T, U1, dec, frames, score);
+    else if (U1 <= 256) rc = launch_viterbi<4, 4>(st, B, w.lpb, w.lpl, act_lens, label_lens, T, U1, dec, frames, score);
+    else if (U1 <= 512) rc = launch_viterbi<8, 2>(st, B, w.lpb, w.lpl, act_lens, label_lens, T, U1, dec, frames, score);
+    else rc = launch_viterbi<16, 1>(st, B, w.lpb, w.lpl, act_lens, label_lens, T, U1, dec, frames, score);
+    if (rc) return rc;
+    TTMI_LAUNCH_CHECK("rnnt_viterbi_kernel");
+    return TTMI_OK;
+}
+
+int ttmi_rnnt_emit_stats(const void* workspace, const int* act_lens, const int* label_lens, int B, int T, int U1, float* expected,
+                         float* mass, void* stream) {
+    TTMI_REQUIRE(workspace && act_lens && label_lens && ((expected && mass) || U1 == 1), "rnnt_emit_stats: null pointer");
+    TTMI_REQUIRE(B > 0 && T > 0 && U1 > 0, "rnnt_emit_stats: bad shape B=%d T=%d U1=%d", B, T, U1);
+    TTMI_REQUIRE(U1 <= 1024, "rnnt_emit_stats: U+1=%d > 1024 unsupported", U1);
+    TTMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "rnnt_emit_stats: workspace must be 8-byte aligned");
+    if (U1 == 1) return TTMI_OK;          // no labels: nothing to write
+    Ws w = carve(const_cast<void*>(workspace), B, T, U1);
+    const long waves = (long)B * (U1 - 1);
+    hipLaunchKernelGGL(rnnt_emit_stats_kernel, dim3(cdiv(waves, 4)), dim3(256), 0, static_cast<hipStream_t>(stream), w.alpha, w.beta, w.ll,
+                       w.lpl, act_lens, label_lens, B, T, U1, expected, mass);
+    TTMI_LAUNCH_CHECK("rnnt_emit_stats_kernel");
     return TTMI_OK;
 }
 

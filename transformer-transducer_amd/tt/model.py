@@ -206,6 +206,62 @@ class _JointLossFn(torch.autograd.Function):
         return (denc * gout, ddec * gout, *rets, None, None, None, None, None, None, None, None, None, None)
 
 
+def _joint_align(joint, enc, dec, labels, act_lens, label_lens, prec, chunk, blank, exp_state, stats):
+    """joint network + loss forward + forced alignment, forward only, chunked over utterances as _JointLossFn.forward chunks: per chunk
+    ttmi_joint_fwd + ttmi_rnnt_loss_fwd + ttmi_rnnt_align (+ ttmi_rnnt_emit_stats), or, with `exp_state` (the JointNet's _ExpShift) valid
+    and the sizes supported, ttmi_joint_fwd_exp + ttmi_rnnt_loss_fwd_exp + the same two calls; the chunk's logits / P buffer is dropped
+    before the next chunk.  The exp-domain form leaves the training state alone: it only READS exp_state.cur (and only when the state is
+    valid), passes no shift_next and raises a flag of its own; chunks whose flag came back set are run again in the plain form (one host
+    read per call).  -> warprnnt_pytorch.AlignResult"""
+    from warprnnt_pytorch import AlignResult
+    with torch.no_grad():
+        enc, dec = enc.detach().contiguous(), dec.detach().contiguous()
+        wf, bf, wp, bp = (t.detach() for t in (joint.forward_layer.weight, joint.forward_layer.bias, joint.project_layer.weight,
+                                               joint.project_layer.bias))
+        B, T, U1 = enc.shape[0], enc.shape[1], dec.shape[1]
+        J, V = wf.shape[0], wp.shape[0]
+        dev = enc.device
+        frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=dev)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        cost = torch.empty(B, dtype=torch.float32, device=dev)
+        expected = torch.empty(B, U1 - 1, dtype=torch.float32, device=dev) if stats else None
+        mass = torch.empty(B, U1 - 1, dtype=torch.float32, device=dev) if stats else None
+        starts = list(range(0, B, chunk))
+        use_exp = exp_state is not None and exp_state.valid
+        flags = torch.zeros(len(starts), dtype=torch.int32, device=dev) if use_exp else None
+
+        def run(i, exp):
+            c0 = starts[i]
+            c1 = min(B, c0 + chunk)
+            n = c1 - c0
+            ws = ops.rnnt_workspace(n, T, U1, dev)
+            lab, al, ll = labels[c0:c1], act_lens[c0:c1], label_lens[c0:c1]
+            if exp:
+                P, rowsum, saved, emis = ops.joint_fwd_exp(enc[c0:c1], dec[c0:c1], wf, bf, wp, bp, prec, exp_state.cur, lab.contiguous(), blank)
+                cost[c0:c1] = ops.rnnt_loss_fwd_exp(P, rowsum, lab, al, ll, blank, ws, exp_state.cur, None, emis, flags[i:i + 1])
+                del P, rowsum, saved, emis
+            else:
+                logits, saved = ops.joint_fwd(enc[c0:c1], dec[c0:c1], wf, bf, wp, bp, prec)
+                cost[c0:c1] = ops.rnnt_loss_fwd(logits, lab, al, ll, blank, ws)
+                del logits, saved
+            frames[c0:c1], score[c0:c1] = ops.rnnt_align(ws, al, ll, n, T, U1)
+            if stats:
+                expected[c0:c1], mass[c0:c1] = ops.rnnt_emit_stats(ws, al, ll, n, T, U1)
+
+        ran_exp = []
+        for i, c0 in enumerate(starts):
+            exp = use_exp and ops.joint_exp_supported(min(B, c0 + chunk) - c0, T, U1, J, V, prec, fwd_only=True)
+            run(i, exp)
+            if exp:
+                ran_exp.append(i)
+        if ran_exp:
+            bad = flags.cpu()                       # a row sum left the range of the shift in use: that chunk again, in the plain form
+            for i in ran_exp:
+                if int(bad[i]) != 0:
+                    run(i, False)
+    return AlignResult(frames, score, cost, expected, mass)
+
+
 def deferred_logits_enabled(config, prec):
     """does Transducer.forward hand out a DeferredLogits handle?  TTMI_DEFERRED_LOGITS=0 / 1 (read per call, like TTMI_PRECISION) or
     config.deferred_logits (True / False) decide; unset: on in the bf16 pipeline (the throughput mode - its logits are 7 GB of bf16 per
@@ -319,6 +375,24 @@ class DeferredLogits(torch.Tensor):
         return _JointLossFn.apply(self._enc, self._dec, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
                                   j.project_layer.bias, labels, act_lens, label_lens, self._prec, int(chunk), reduction,
                                   j.exp_shift_state(self._enc.device) if exp else None, grad, int(blank), fastemit_lambda)
+
+    def rnnt_align(self, labels, act_lens, label_lens, blank=0, *, stats=False):
+        """forced alignment on this handle's logits without forming them (called by warprnnt_pytorch.rnnt_align; arguments already
+        certified there): the chunked forward-only loop of Transducer.align.  None when the handle was already used as a tensor (the
+        caller then aligns the real logits)."""
+        if self._real is not None:
+            return None
+        j = self._joint
+        B, T, U1 = self.shape[0], self.shape[1], self.shape[2]
+        ops.weights_fresh()
+        exp = self._prec == 1 and os.environ.get("TTMI_DEFERRED_EXP", "1") != "0"
+        st = j.exp_shift_state(self._enc.device) if exp else None
+        exp = exp and st.valid
+        chunk = j.default_loss_chunk(B, T, U1, exp, self._prec)
+        if exp and not ops.joint_exp_supported(chunk, T, U1, j.forward_layer.out_features, j.project_layer.out_features, self._prec, fwd_only=True):
+            exp, chunk = False, j.default_loss_chunk(B, T, U1, False, self._prec)
+        return _joint_align(j, self._enc, self._dec, labels, act_lens, label_lens, self._prec, int(chunk), int(blank), st if exp else None,
+                            stats)
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
@@ -518,6 +592,40 @@ class Transducer(nn.Module):
                                   j.project_layer.bias, labels, al, ll, prec, int(chunk), reduction,
                                   j.exp_shift_state(enc_state.device) if exp_domain and prec == 1 else None, torch.is_grad_enabled(), 0,
                                   fastemit_lambda)
+
+    def align(self, inputs, inputs_length, targets, targets_length, chunk=None, check_lengths=True, exp_domain=False, *, stats=False):
+        """Forced alignment of `targets` to `inputs`: the best path through the RNN-T lattice, without materialising the logits (the chunked
+        joint + loss forward of `loss()`, forward only, under no_grad; the reference has no counterpart).  -> warprnnt_pytorch.AlignResult:
+        `frames` int32 [B, U] (frames[b][u] = the frame at which label u+1 of utterance b is emitted, non-decreasing, -1 for u >= U_b),
+        `score` [B] (log-probability of that path), `cost` [B] (-log P(y|x), what loss(reduction='none') returns) and, with stats=True,
+        `expected_frames` / `mass` [B, U] (posterior mean emission frame of each label; total emission posterior, 1 for a healthy lattice).
+        Tie rule: a label move is taken only when strictly better than the blank move (include/ttmi.h, ttmi_rnnt_align).
+
+        exp_domain=True (bf16 mode, training-sized chunks, and only once a training step has made the module's shift valid; the plain form
+        otherwise): the exp-domain joint + loss forward.  It does not disturb training: the shift state of the joint (_ExpShift cur / nxt /
+        flag / valid) is only read; an out-of-range chunk is detected by a flag of this call's own and run again in the plain form.
+
+        The encoders run under no_grad in whatever mode the module is in: call it in eval() mode.  On a module in train() with
+        dropout > 0 the alignment is taken on dropped-out encoder states and the call draws from the dropout generator like any other
+        forward, so "does not disturb training" is a statement about the shift state only."""
+        from warprnnt_pytorch import check_lengths as certify
+        labels, al, ll = (t.to(dtype=torch.int32) for t in (targets, inputs_length, targets_length))
+        certify(labels.contiguous(), al.contiguous(), ll.contiguous(), inputs.shape[0], 0, targets.shape[1] + 1, False)
+        if not inputs.is_cuda:
+            raise ValueError("Transducer.align: inputs must live on the GPU (the MI355X build has no CPU path)")
+        with torch.no_grad():
+            enc_state, dec_state = self._encode(inputs, targets)
+        B, T, U1 = enc_state.shape[0], enc_state.shape[1], dec_state.shape[1]
+        labels, al, ll = (t.to(device=enc_state.device).contiguous() for t in (labels, al, ll))
+        certify(labels, al, ll, B, T, U1, check_lengths)
+        ops.weights_fresh()
+        prec = default_precision()
+        st = self.joint.exp_shift_state(enc_state.device) if exp_domain and prec == 1 else None
+        if st is not None and not st.valid:
+            st = None
+        if chunk is None:
+            chunk = self.default_loss_chunk(B, T, U1, st is not None)
+        return _joint_align(self.joint, enc_state, dec_state, labels, al, ll, prec, int(chunk), 0, st, stats)
 
     def default_loss_chunk(self, B, T, U1, exp_domain=False):
         """utterances per chunk of `loss()` (JointNet.default_loss_chunk)"""

@@ -594,6 +594,34 @@ def rnnt_shift_seed(workspace, act_lens, label_lens, B, T, U1, shift_next):
           "ttmi_rnnt_shift_seed")
 
 
+def rnnt_align(workspace, act_lens, label_lens, B, T, U1):
+    """best path through the lattice a finished rnnt_loss_fwd / rnnt_loss_fwd_exp left in `workspace` (read only) ->
+    (frames int32 [B, U1-1]: the frame at which label u+1 is emitted, -1 for u >= U_b; score f32 [B]: the path's log-probability).
+    The label move is taken only when strictly greater (a tie goes to blank); include/ttmi.h, ttmi_rnnt_align"""
+    _need_cuda(workspace, act_lens, label_lens)
+    _trace("rnnt_align", B, T, U1)
+    f = lib().ttmi_rnnt_align_workspace_bytes
+    f.restype = ctypes.c_size_t
+    aws = torch.empty((f(c_int(B), c_int(T), c_int(U1)) + 7) // 8, dtype=torch.int64, device=workspace.device)
+    frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=workspace.device)
+    score = torch.empty(B, dtype=torch.float32, device=workspace.device)
+    check(lib().ttmi_rnnt_align(_p(workspace), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U1), _p(aws), _p(frames), _p(score),
+                                _stream()), "ttmi_rnnt_align")
+    return frames, score
+
+
+def rnnt_emit_stats(workspace, act_lens, label_lens, B, T, U1):
+    """per label, from the alpha / beta of a finished forward in `workspace` (read only) -> (expected f32 [B, U1-1]: expected emission frame,
+    -1 for u >= U_b; mass f32 [B, U1-1]: total emission posterior, 1 for a healthy lattice, 0 for u >= U_b)"""
+    _need_cuda(workspace, act_lens, label_lens)
+    _trace("rnnt_emit_stats", B, T, U1)
+    expected = torch.empty(B, U1 - 1, dtype=torch.float32, device=workspace.device)
+    mass = torch.empty(B, U1 - 1, dtype=torch.float32, device=workspace.device)
+    check(lib().ttmi_rnnt_emit_stats(_p(workspace), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U1), _p(expected), _p(mass),
+                                     _stream()), "ttmi_rnnt_emit_stats")
+    return expected, mass
+
+
 def rnnt_loss_bwd_exp(P, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, fastemit_lambda=0.0):
     """patches P in place -> (srow f32 [rows], srow16 bf16 [rows]): d logits = srow[r] * P[r, :]"""
     fe = check_fastemit(fastemit_lambda)

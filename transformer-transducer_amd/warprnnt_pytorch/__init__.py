@@ -13,15 +13,21 @@ the batch and returns shape [1].  The arithmetic runs in libttmi's HIP kernels
 regularisation (Yu et al., ICASSP 2021) as the transducer-loss libraries
 expose it: the gradient favours emitting a label over emitting blank, the
 returned cost stays -log P(y|x).  Formula: include/ttmi.h.
+
+`rnnt_align` (no counterpart in warp-transducer, which returns costs only) is
+forced alignment on the same arguments: the best path through the lattice
+(frame of every label's emission), its log-probability, the cost, and on
+request the expected emission frame of every label.
 """
 import os
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 
 from ttmi import ops
 
-__all__ = ["RNNTLoss", "rnnt_loss", "check_lengths"]
+__all__ = ["RNNTLoss", "rnnt_loss", "rnnt_align", "AlignResult", "check_lengths"]
 
 
 _max_cache = {}     # id(tensor) -> (weakref, tensor._version, max): the length check costs a device-to-host sync; a lengths tensor that
@@ -125,6 +131,47 @@ def rnnt_loss(acts, labels, act_lens, label_lens, blank=0, reduction="mean", che
             return out
         acts = acts.materialize()           # (per-utterance costs with gradients, or a handle that was already used as a tensor)
     return _RNNTLossFn.apply(acts, labels, act_lens, label_lens, int(blank), reduction, fastemit_lambda)
+
+
+class AlignResult(NamedTuple):
+    """frames int32 [B, U]: frames[b][u] = the frame at which label u+1 of utterance b is emitted on the best path (the path's move
+    (t, u) -> (t, u+1)), non-decreasing in u, -1 for u >= U_b; score f32 [B]: log-probability of that path; cost f32 [B]: -log P(y|x), the
+    bits RNNTLoss(reduction='none') returns; with stats=True expected_frames f32 [B, U] (posterior mean emission frame, -1 for u >= U_b) and
+    mass f32 [B, U] (total emission posterior of the label: 1 for a healthy lattice, 0 for u >= U_b), else None"""
+    frames: torch.Tensor
+    score: torch.Tensor
+    cost: torch.Tensor
+    expected_frames: Optional[torch.Tensor] = None
+    mass: Optional[torch.Tensor] = None
+
+
+def rnnt_align(acts, labels, act_lens, label_lens, blank=0, check_lengths=None, *, stats=False):
+    """Forced alignment: arguments as rnnt_loss -> AlignResult.  Forward only (runs under no_grad).  Tie rule: a label move is taken only
+    when strictly better than the blank move (include/ttmi.h, ttmi_rnnt_align).  A DeferredLogits handle goes through the fused joint +
+    loss path instead of being materialised, as in rnnt_loss."""
+    if check_lengths is None:
+        check_lengths = os.environ.get("TTMI_CHECK_LENGTHS", "1") != "0"
+    labels, act_lens, label_lens = (t.to(acts.device) for t in (labels, act_lens, label_lens))
+    _certify(acts, labels, act_lens, label_lens, check_lengths)
+    if not acts.is_cuda:
+        raise ValueError("rnnt_align: acts must live on the GPU (the MI355X build has no CPU path)")
+    with torch.no_grad():
+        fused = getattr(acts, "rnnt_align", None)
+        if fused is not None:
+            out = fused(labels, act_lens, label_lens, int(blank), stats=bool(stats))
+            if out is not None:
+                return out
+            acts = acts.materialize()
+        acts = acts.detach()
+        B, T, U1, _ = acts.shape
+        acts_c = acts if ops.row_pitch(acts) is not None else acts.contiguous()
+        ws = ops.rnnt_workspace(B, T, U1, acts.device)
+        cost = ops.rnnt_loss_fwd(acts_c, labels, act_lens, label_lens, int(blank), ws)
+        frames, score = ops.rnnt_align(ws, act_lens, label_lens, B, T, U1)
+        expected = mass = None
+        if stats:
+            expected, mass = ops.rnnt_emit_stats(ws, act_lens, label_lens, B, T, U1)
+    return AlignResult(frames, score, cost, expected, mass)
 
 
 class RNNTLoss(torch.nn.Module):
