@@ -1459,29 +1459,44 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(const TS* __rest
     }
 }
 
-// greedy scan: rows of logits (f32 or bf16, pitch ld); out[0] = first row whose argmax != blank (or n), out[1] = that argmax.
-// One wave per row computes the argmax (first maximal index, like torch.argmax); the rows' results go through a single
-// atomicMin on the packed (row << 32 | token) key, so one 8-byte D2H read tells the host where the next symbol is.
+// argmax order of the greedy scans = torch.argmax's: NaN is larger than every number, equal values (and NaN against NaN) go to the lower
+// index.  A lane starts from (-inf, 0x7fffffff), which loses to every real entry - to -inf too, by its index - so a row of V >= 1 entries
+// always ends on an index in [0, V): an all -inf row on 0, a row with NaN on its first NaN.
+__device__ __forceinline__ bool argmax_takes(float x, int xi, float best, int bi) {
+    const bool xn = x != x, bn = best != best;
+    return (x > best) | (xn & !bn) | (((x == best) | (xn & bn)) & (xi < bi));
+}
+
+// one wave, one row: every lane returns the row's argmax in that order
 template <typename TL>
-__global__ __launch_bounds__(256) void greedy_scan_kernel(const TL* __restrict__ logits, long ld, int n, int V, int blank,
-                                                          unsigned long long* __restrict__ out) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (row >= n) return;
-    const TL* r = logits + (long)row * ld;
+__device__ __forceinline__ int wave_row_argmax(const TL* __restrict__ r, int V, int lane) {
     float best = -INFINITY;
     int bi = 0x7fffffff;
     for (int v = lane; v < V; v += 64) {
         float x;
         if constexpr (sizeof(TL) == 4) x = r[v];
         else x = bf16_to_f32(r[v]);
-        if (x > best) { best = x; bi = v; }
+        if (argmax_takes(x, v, best, bi)) { best = x; bi = v; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ob = __shfl_xor(best, o, 64);
         const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        if (argmax_takes(ob, oi, best, bi)) { best = ob; bi = oi; }
     }
+    return bi;
+}
+
+// greedy scan: rows of logits (f32 or bf16, pitch ld); out[0] = first row whose argmax != blank (or n), out[1] = that argmax.
+// One wave per row computes the argmax (first maximal index, like torch.argmax, rows without a finite maximum included); the rows' results
+// go through a single atomicMin on the packed (row << 32 | token) key, so one 8-byte D2H read tells the host where the next symbol is.
+template <typename TL>
+__global__ __launch_bounds__(256) void greedy_scan_kernel(const TL* __restrict__ logits, long ld, int n, int V, int blank,
+                                                          unsigned long long* __restrict__ out) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n) return;
+    const TL* r = logits + (long)row * ld;
+    const int bi = wave_row_argmax(r, V, lane);
     if (lane == 0 && bi != blank) atomicMin(out, ((unsigned long long)row << 32) | (unsigned)bi);
 }
 
@@ -1499,20 +1514,7 @@ __global__ __launch_bounds__(256) void greedy_scan_batch_kernel(const TL* __rest
     const int b = row / n, r = row - b * n;
     if (!need[b] || t[b] + r >= T_len[b]) return;       // (wave-uniform) this utterance has its symbol already, or the frame does not exist
     const TL* p = logits + (long)row * ld;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int v = lane; v < V; v += 64) {
-        float x;
-        if constexpr (sizeof(TL) == 4) x = p[v];
-        else x = bf16_to_f32(p[v]);
-        if (x > best) { best = x; bi = v; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
+    const int bi = wave_row_argmax(p, V, lane);
     if (lane == 0 && bi != blank) atomicMin(key + b, ((unsigned long long)r << 32) | (unsigned)bi);
 }
 // one thread per utterance: consume key[b].  A symbol found: append it to the history (column n_hist), move past its frame, this utterance
