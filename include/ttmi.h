@@ -273,6 +273,28 @@ int ttmi_greedy_scan_batch(const void* logits, int dtype, long ld, int B, int n,
                            const int* need, unsigned long long* key, void* stream);
 int ttmi_greedy_advance(unsigned long long* key, int B, int n, int n_hist, long* hist, long ld_hist, int* t, const int* T_len, int* need,
                         int* done, int* count, int* flags, void* stream);
+/* The same pair with what the scan's logits also say about each decision (Transducer.decode_batch(details=True)): where every token was
+ * emitted, how probable it was, and the log-probability of the whole greedy path.
+ * ttmi_greedy_scan_batch_lp: ttmi_greedy_scan_batch (same rows skipped, key bit-identical) that also writes lp (device f32 [B, n, 2]) for every
+ * row it walks: lp[b][r][0] = log P(blank) = x[blank] - lse, lp[b][r][1] = log P(argmax) = x[argmax] - lse, lse = the row's log-sum-exp, taken in
+ * the same single pass over the row in f32 (bf16 logits widened exactly).  The two are equal when the argmax is the blank.  Rows the scan skips
+ * (need[b] == 0, t[b] + r >= T_len[b]) are NOT written.  A row whose log-sum-exp is not finite (it holds a NaN or +inf, or is all -inf) gives NaN
+ * in both entries; its key is ttmi_greedy_scan_batch's.  A `blank` outside [0, V) is a blank of probability 0: entry 0 = -inf.
+ * ttmi_greedy_advance_lp: ttmi_greedy_advance (same transitions, same flags) that also, for every utterance with need[b], t0 = t[b] and
+ * c = count[b] before the update: symbol found at row r -> frames[b][c] = t0 + r, tok_lp[b][c] = lp[b][r][1], score[b] += sum over r' < r of
+ * lp[b][r'][0], + lp[b][r][1]; none -> score[b] += sum of lp[b][r'][0] over the rows with t0 + r' < T_len[b].  frames i32 / tok_lp f32
+ * [B, ld_det], count[b] < ld_det required; score: device f64 [B], the caller zeroes it before the first block.  The sum is taken by the
+ * utterance's one thread, in row order, in f64: no floating-point atomics, two runs give the same bits.
+ * score[b] is the log-probability of the decisions the greedy decoder took: each of the utterance's T_b frames contributes one term, blank's
+ * log-probability against the label state current at that frame on a frame that does not emit, the symbol's on a frame that does (the emitting
+ * frame is consumed: at most one symbol per frame).  That is the path of this decoder, NOT a path of the RNN-T lattice (the lattice follows a
+ * label with a blank on the same frame): it is not comparable with ttmi_rnnt_align's score.
+ * Neither call allocates, synchronises with the host or issues a memset node; both may be captured in a HIP graph. */
+int ttmi_greedy_scan_batch_lp(const void* logits, int dtype, long ld, int B, int n, int V, int blank, const int* t, const int* T_len,
+                              const int* need, unsigned long long* key, float* lp, void* stream);
+int ttmi_greedy_advance_lp(unsigned long long* key, int B, int n, int n_hist, long* hist, long ld_hist, int* t, const int* T_len, int* need,
+                           int* done, int* count, int* flags, const float* lp, int* frames, float* tok_lp, long ld_det, double* score,
+                           void* stream);
 
 /* ---- feature front-end on the GPU: replaces the data loader's per-utterance numpy code.
  * ttmi_logmel: get_feature / get_feature2 (tt/utils.py:182-207: librosa.feature.melspectrogram(y, sr, n_fft=512, hop_length=160, n_mels), then

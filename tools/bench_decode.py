@@ -6,7 +6,10 @@ beside it (token check + CPU time); the full-size token parity test is tests/tes
 A random-init model emits a symbol on (nearly) every frame, the worst case for the reference's full-history label-encoder
 recompute; `--emit-rate r` raises the joint's blank bias so that about r of the frames emit (r = 0.1 ~ U = 50 symbols per T = 500).
 
-    python tools/bench_decode.py [--utts 8] [--T 500] [--emit-rate 0.1] [--precision fp32]
+    python tools/bench_decode.py [--utts 8] [--T 500] [--emit-rate 0.1] [--precision fp32] [--details]
+
+--details also times decode_batch(details=True) (emission frames, token log-probabilities, path score from the scan's own pass over the logits)
+on the same encoder states, after the plain run and a warm-up of its own; the plain figures are taken exactly as without the flag.
 """
 import argparse
 import json
@@ -22,9 +25,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "transformer-transducer_amd"))
 
 
-def run(utts=8, T=500, emit_rate=0.1, precision="fp32", block=None):
+def run(utts=8, T=500, emit_rate=0.1, precision="fp32", block=None, details=False):
     """returns (result dict, model, inputs [utts,T,d], lengths, hypotheses)"""
-    args = argparse.Namespace(utts=utts, T=T, emit_rate=emit_rate, precision=precision, block=block)
+    args = argparse.Namespace(utts=utts, T=T, emit_rate=emit_rate, precision=precision, block=block, details=details)
     os.environ["TTMI_PRECISION"] = args.precision
     from bench import c2_config
     from tt.model import Transducer
@@ -75,6 +78,13 @@ def run(utts=8, T=500, emit_rate=0.1, precision="fp32", block=None):
         torch.cuda.synchronize()
         t_dec = time.perf_counter() - t0
         ops.greedy_advance = orig
+        if args.details:
+            model.decode_batch(enc_states, lens, block=args.block, details=True)      # warm-up: first launches of the two _lp kernels
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            det = model.decode_batch(enc_states, lens, block=args.block, details=True)
+            torch.cuda.synchronize()
+            t_det = time.perf_counter() - t0
     nsym = sum(len(h) for h in hyps)
     out = {"workload": "greedy decode, C2 model (12/6 layers, V=4334), %d utt x T=%d, %s, emit rate target %.2f"
                        % (args.utts, args.T, args.precision, args.emit_rate),
@@ -91,6 +101,11 @@ def run(utts=8, T=500, emit_rate=0.1, precision="fp32", block=None):
                                        "tokens_identical_to_batched": hyps1 == hyps,
                                        "host_syncs_per_utt_approx": round((nsym + args.utts * -(-args.T // (args.block or 64))) / args.utts, 1)}}
 
+    if args.details:
+        out["details"] = {"decode_ms_per_utt": round(1e3 * t_det / args.utts, 2), "utt_per_s": round(args.utts / (t_enc + t_det), 3),
+                          "tokens_identical_to_plain": [r.tokens for r in det] == hyps,
+                          "mean_token_logprob": round(sum(sum(r.logprobs) for r in det) / max(nsym, 1), 4),
+                          "mean_score_per_frame": round(sum(r.score for r in det) / (args.utts * args.T), 4)}
     return out, model, inputs, lens, hyps
 
 
@@ -101,8 +116,9 @@ def main():
     ap.add_argument("--emit-rate", type=float, default=0.1)
     ap.add_argument("--precision", default="fp32", choices=["bf16", "fp32"])
     ap.add_argument("--block", type=int, default=None, help="frames per joint call (default: 64, or what fits one round of projection tiles)")
+    ap.add_argument("--details", action="store_true", help="also time decode_batch(details=True) on the same encoder states")
     a = ap.parse_args()
-    print(json.dumps(run(a.utts, a.T, a.emit_rate, a.precision, a.block)[0]), flush=True)
+    print(json.dumps(run(a.utts, a.T, a.emit_rate, a.precision, a.block, a.details)[0]), flush=True)
 
 
 if __name__ == "__main__":

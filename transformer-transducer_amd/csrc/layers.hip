@@ -1657,6 +1657,17 @@ int ttmi_greedy_advance(unsigned long long* key, int B, int n, int n_hist, long*
                         int* done, int* count, int* flags, void* stream) {
     return greedy_advance(key, B, n, n_hist, hist, ld_hist, t, T_len, need, done, count, flags, static_cast<hipStream_t>(stream));
 }
+// ... with per-token emission frames, log-probabilities and the score of the greedy path (decode_batch(details=True), ttmi.h)
+int ttmi_greedy_scan_batch_lp(const void* logits, int dtype, long ld, int B, int n, int V, int blank, const int* t, const int* T_len,
+                              const int* need, unsigned long long* key, float* lp, void* stream) {
+    return greedy_scan_batch_lp(logits, dtype, ld, B, n, V, blank, t, T_len, need, key, lp, static_cast<hipStream_t>(stream));
+}
+int ttmi_greedy_advance_lp(unsigned long long* key, int B, int n, int n_hist, long* hist, long ld_hist, int* t, const int* T_len, int* need,
+                           int* done, int* count, int* flags, const float* lp, int* frames, float* tok_lp, long ld_det, double* score,
+                           void* stream) {
+    return greedy_advance_lp(key, B, n, n_hist, hist, ld_hist, t, T_len, need, done, count, flags, lp, frames, tok_lp, ld_det, score,
+                             static_cast<hipStream_t>(stream));
+}
 
 // ------------------------------------------------------------------ embedding (tt/decoder.py:26,39)
 int ttmi_embed_fwd(const long* tokens, const float* W, long n, int d, int V, float* out, void* stream) {

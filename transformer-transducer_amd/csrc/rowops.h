@@ -107,6 +107,12 @@ int greedy_scan_batch(const void* logits, int dtype, long ld, int B, int n, int 
                       unsigned long long* key, hipStream_t st);
 int greedy_advance(unsigned long long* key, int B, int n, int n_hist, long* hist, long ld_hist, int* t, const int* T_len, int* need, int* done,
                    int* count, int* flags, hipStream_t st);
+// the same pair for decode_batch(details=True): the scan also writes lp [B, n, 2] = log P(blank), log P(argmax) of every row it walks, the
+// advance books emission frames, token log-probabilities and the f64 score of the greedy path (ttmi.h)
+int greedy_scan_batch_lp(const void* logits, int dtype, long ld, int B, int n, int V, int blank, const int* t, const int* T_len, const int* need,
+                         unsigned long long* key, float* lp, hipStream_t st);
+int greedy_advance_lp(unsigned long long* key, int B, int n, int n_hist, long* hist, long ld_hist, int* t, const int* T_len, int* need, int* done,
+                      int* count, int* flags, const float* lp, int* frames, float* tok_lp, long ld_det, double* score, hipStream_t st);
 // batched transpose to bf16: for z = z1*nz2+z2, dst[z][c][r] = src[z1*s1 + z2*s2 + r*ld + c] (r < R, c < C), dst pitch ldd >= R with
 // zero fill in [R, ldd), dst slab = C*ldd.  src_dtype 0 = f32, 1 = bf16.  Produces the K-major operands of the position products.
 int transpose_bf16_batched(const void* src, int src_dtype, long ld, int nz1, int nz2, long s1, long s2, int R, int C, bf16_t* dst,

@@ -1543,6 +1543,97 @@ __global__ void greedy_advance_kernel(unsigned long long* __restrict__ key, int 
     if (!done[b]) atomicAdd(flags + 1, 1);
 }
 
+// ---- the same two kernels for decode_batch(details=True): the scan also leaves log P(blank) and log P(argmax) of every row it walks, the
+// advance turns them into per-token emission frames / log-probabilities and the score of the greedy path.
+// greedy_scan_batch_lp: greedy_scan_batch_kernel (same grid, same skipped rows, same argmax code, so the same key bits) whose single pass over
+// the row also carries, per lane, the running pair (m, s) = (max, sum of exp(x - m)), rescaled when the max moves (one exp per logit: of
+// -|x - m|); the pairs are merged with the shuffles of the argmax.  No second pass, no LDS.  lp[row] = (x[blank] - lse, x[argmax] - lse)
+// with lse = m + log s, the blank's value picked up by the lane that read it and the argmax's carried by the reduction (`best`).  An entry of
+// -inf adds nothing; a NaN makes s NaN, a +inf makes m +inf, an all -inf row leaves (-inf, 0): lse is not finite and both entries are NaN.
+// A blank outside [0, V) (no column is blank: every row emits) has probability 0, entry 0 = -inf.
+template <typename TL>
+__global__ __launch_bounds__(256) void greedy_scan_batch_lp_kernel(const TL* __restrict__ logits, long ld, int B, int n, int V, int blank,
+                                                                   const int* __restrict__ t, const int* __restrict__ T_len,
+                                                                   const int* __restrict__ need, unsigned long long* __restrict__ key,
+                                                                   float* __restrict__ lp) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= B * n) return;
+    const int b = row / n, r = row - b * n;
+    if (!need[b] || t[b] + r >= T_len[b]) return;       // (wave-uniform) as in greedy_scan_batch_kernel; lp[row] is left alone
+    const TL* p = logits + (long)row * ld;
+    float best = -INFINITY, m = -INFINITY, s = 0.f, xb = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int v = lane; v < V; v += 64) {
+        float x;
+        if constexpr (sizeof(TL) == 4) x = p[v];
+        else x = bf16_to_f32(p[v]);
+        if (argmax_takes(x, v, best, bi)) { best = x; bi = v; }
+        if (v == blank) xb = x;
+        if (x != -INFINITY) {                            // (-inf against m = -inf would be exp(NaN))
+            const float e = __expf(-fabsf(x - m));       // NaN for a NaN entry and for +inf against m = +inf: s is NaN from there on
+            if (x > m) { s = s * e + 1.f; m = x; }
+            else s += e;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+        if (argmax_takes(ob, oi, best, bi)) { best = ob; bi = oi; }
+        const float nm = fmaxf(m, om);                   // (m is never NaN; equal maxima, -inf and +inf included, are not rescaled)
+        s = s * (m == nm ? 1.f : __expf(m - nm)) + os * (om == nm ? 1.f : __expf(om - nm));
+        m = nm;
+    }
+    xb = (blank >= 0 && blank < V) ? __shfl(xb, blank & 63, 64) : -INFINITY;
+    if (lane == 0) {
+        if (bi != blank) atomicMin(key + b, ((unsigned long long)r << 32) | (unsigned)bi);
+        const float lse = m + logf(s);
+        const bool finite = lse - lse == 0.f;
+        lp[2 * (long)row] = finite ? xb - lse : NAN;
+        lp[2 * (long)row + 1] = finite ? best - lse : NAN;
+    }
+}
+// greedy_advance_lp: greedy_advance_kernel (same transitions, same flags) that also books what the consumed block decided.  The greedy path
+// takes one decision per frame: blank on the frames in front of the emission, the symbol on the emitting frame (which is consumed: this is the
+// decoder's own "at most one symbol per frame" path, not a path of the RNN-T lattice).  score[b] accumulates their log-probabilities in f64,
+// added by the utterance's one thread in row order: no floating-point atomics, the same bits in every run.
+__global__ void greedy_advance_lp_kernel(unsigned long long* __restrict__ key, int B, int n, int n_hist, long* __restrict__ hist, long ld_hist,
+                                         int* __restrict__ t, const int* __restrict__ T_len, int* __restrict__ need, int* __restrict__ done,
+                                         int* __restrict__ count, int* __restrict__ flags, const float* __restrict__ lp,
+                                         int* __restrict__ frames, float* __restrict__ tok_lp, long ld_det, double* __restrict__ score) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const unsigned long long k = key[b];
+    key[b] = (unsigned long long)n << 32;
+    if (need[b]) {
+        const int row = (int)(k >> 32), t0 = t[b];
+        const float* q = lp + 2 * (long)b * n;
+        double sc = score[b];
+        if (row < n) {
+            for (int r = 0; r < row; ++r) sc += (double)q[2 * r];
+            sc += (double)q[2 * row + 1];
+            const int c = count[b];
+            if (c < ld_det) {                                      // (the contract asks for it; never write past the row)
+                frames[(long)b * ld_det + c] = t0 + row;
+                tok_lp[(long)b * ld_det + c] = q[2 * row + 1];
+            }
+            hist[(long)b * ld_hist + n_hist] = (long)(unsigned)(k & 0xffffffffu);
+            t[b] = t0 + row + 1;                                   // the emitting frame is consumed (at most one symbol per frame)
+            count[b] = c + 1;
+            need[b] = 0;
+        } else {
+            const int left = T_len[b] - t0;                        // the rows of this block the scan walked: frames inside the utterance
+            for (int r = 0; r < n && r < left; ++r) sc += (double)q[2 * r];
+            t[b] = t0 + n;
+            if (t[b] >= T_len[b]) { need[b] = 0; done[b] = 1; }
+        }
+        score[b] = sc;
+    }
+    if (need[b]) atomicAdd(flags, 1);
+    if (!done[b]) atomicAdd(flags + 1, 1);
+}
+
 }  // namespace
 
 int greedy_scan_batch(const void* logits, int dtype, long ld, int B, int n, int V, int blank, const int* t, const int* T_len, const int* need,
@@ -1565,6 +1656,31 @@ int greedy_advance(unsigned long long* key, int B, int n, int n_hist, long* hist
     if (fill_zero(flags, 2 * sizeof(int), st) != TTMI_OK) return TTMI_EINVAL;
     hipLaunchKernelGGL(greedy_advance_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, key, B, n, n_hist, hist, ld_hist, t, T_len, need, done, count, flags);
     TTMI_LAUNCH_CHECK("greedy_advance_kernel");
+    return TTMI_OK;
+}
+
+int greedy_scan_batch_lp(const void* logits, int dtype, long ld, int B, int n, int V, int blank, const int* t, const int* T_len, const int* need,
+                         unsigned long long* key, float* lp, hipStream_t st) {
+    TTMI_REQUIRE(logits && t && T_len && need && key && lp, "greedy_scan_batch_lp: null pointer");
+    TTMI_REQUIRE(B > 0 && n > 0 && V > 0 && ld >= V, "greedy_scan_batch_lp: bad arguments");
+    if (dtype == 0)
+        hipLaunchKernelGGL(greedy_scan_batch_lp_kernel<float>, dim3(cdiv((long)B * n, 4)), dim3(256), 0, st, static_cast<const float*>(logits), ld, B, n,
+                           V, blank, t, T_len, need, key, lp);
+    else
+        hipLaunchKernelGGL(greedy_scan_batch_lp_kernel<bf16_t>, dim3(cdiv((long)B * n, 4)), dim3(256), 0, st, static_cast<const bf16_t*>(logits), ld, B,
+                           n, V, blank, t, T_len, need, key, lp);
+    TTMI_LAUNCH_CHECK("greedy_scan_batch_lp_kernel");
+    return TTMI_OK;
+}
+
+int greedy_advance_lp(unsigned long long* key, int B, int n, int n_hist, long* hist, long ld_hist, int* t, const int* T_len, int* need, int* done,
+                      int* count, int* flags, const float* lp, int* frames, float* tok_lp, long ld_det, double* score, hipStream_t st) {
+    TTMI_REQUIRE(key && hist && t && T_len && need && done && count && flags && lp && frames && tok_lp && score, "greedy_advance_lp: null pointer");
+    TTMI_REQUIRE(B > 0 && n > 0 && n_hist >= 1 && n_hist < ld_hist && ld_det > 0, "greedy_advance_lp: bad arguments");
+    if (fill_zero(flags, 2 * sizeof(int), st) != TTMI_OK) return TTMI_EINVAL;
+    hipLaunchKernelGGL(greedy_advance_lp_kernel, dim3(cdiv(B, 64)), dim3(64), 0, st, key, B, n, n_hist, hist, ld_hist, t, T_len, need, done, count, flags,
+                       lp, frames, tok_lp, ld_det, score);
+    TTMI_LAUNCH_CHECK("greedy_advance_lp_kernel");
     return TTMI_OK;
 }
 

@@ -1,5 +1,6 @@
 """Transducer / JointNet with the reference's API surface (tt/model.py): .encoder/.decoder/.joint,
 forward(inputs[B,T,d], targets[B,U]) -> logits[B,T,U+1,V], decode/recognize (greedy), beam search."""
+import collections
 import copy
 import heapq
 import os
@@ -430,6 +431,15 @@ class DeferredLogits(torch.Tensor):
 _META_FUNCTIONS = _meta_functions()
 
 
+DecodeResult = collections.namedtuple("DecodeResult", ["tokens", "frames", "logprobs", "score"])
+DecodeResult.__doc__ = """What greedy decoding returns per utterance with details=True (decode / decode_batch / recognize): `tokens` (list of int, what
+details=False returns), `frames` (list of int, the frame at which each token was emitted: strictly increasing, < T_b), `logprobs` (list of float,
+log P(token) on its emission frame) and `score` (float): the log-probability of the decisions the greedy decoder took, one term per frame of the
+utterance - blank's log-probability against the label state current at that frame on a frame that does not emit, the token's on a frame that does.
+That is the path of this decoder (at most one symbol per frame, the emitting frame is consumed), NOT a path of the RNN-T lattice, which follows a
+label with a blank on the same frame: `score` is not comparable with `Transducer.align(...).score`."""
+
+
 class JointNet(nn.Module):
     """logits = project_layer(tanh(forward_layer(cat(enc, dec)))) evaluated in split-weight form
     (forward_layer.weight = [W_enc | W_dec]); accepts [B,T,de]/[B,U,dd] (lattice) or two 1-D vectors (decode)."""
@@ -699,12 +709,15 @@ class Transducer(nn.Module):
         return MaskSpec(2, left=int(s.get("left", 0)), right=int(s.get("right", 0)))
 
     @torch.no_grad()
-    def decode(self, enc_state, lengths, block=64):
+    def decode(self, enc_state, lengths, block=64, details=False):
         """Greedy: <= 1 symbol per frame, label encoder re-run on the whole history WITHOUT look-ahead mask (tt/model.py:70-90).
         Same token sequence as the reference's per-frame loop, but frames are scored `block` at a time against the current
         label state and the first non-blank frame is found on the device (ttmi_greedy_scan): one host sync per emitted
         symbol instead of one per frame.  The label-encoder re-runs replay captured graphs (one per history length, see
-        _LabelStateGraphs)."""
+        _LabelStateGraphs).  details=True: -> DecodeResult (tokens, emission frames, token log-probabilities, path score), from
+        `decode_batch`'s device-side bookkeeping on a batch of one."""
+        if details:
+            return self.decode_batch(enc_state[None], [int(lengths)], block=block, details=True)[0]
         token_list = [0]
         dev = enc_state.device
         T = int(lengths)
@@ -747,7 +760,7 @@ class Transducer(nn.Module):
         return g
 
     @torch.no_grad()
-    def decode_batch(self, enc_states, lengths, block=None):
+    def decode_batch(self, enc_states, lengths, block=None, details=False):
         """Greedy decoding of EVERY utterance of a batch at once: the token lists `decode(enc_states[b], lengths[b])` returns, for all b
         (tt/model.py:92-108 loops over the utterances, one host round trip per frame each).  The batch advances in lockstep over SYMBOL
         steps: in step s every utterance still decoding looks for its next non-blank frame (blocks of `block` frames from its own position,
@@ -759,7 +772,15 @@ class Transducer(nn.Module):
         utterance.  Utterances that have run out of frames LEAVE the batch (no extra host round trip: the count of the living comes with the
         flags, the rows from a stable sort on the device), so the long tail of a batch - the longest hypothesis of 32 synthetic utterances
         has 105 symbols, the mean 50 - runs on a handful of rows instead of 32.  Same arithmetic per utterance as `decode`: same tokens.
-        block = frames scored per joint call (default 64)."""
+        block = frames scored per joint call (default 64).
+
+        details=True: -> a list of DecodeResult.  ttmi_greedy_scan_batch_lp / ttmi_greedy_advance_lp run in place of the plain pair: the scan's
+        one pass over each row of logits also yields log P(blank) and log P(argmax), the advance books the emission frame and log-probability
+        of every token and the f64 log-probability of the greedy path (DecodeResult for what that score is and is not).  Same joint and
+        label-encoder calls, same host reads; the details follow the rows through the shrinking batch like the histories and come back in
+        the one transfer at the end."""
+        if details and not enc_states.is_cuda:
+            raise ValueError("decode_batch(details=True): enc_states must live on the GPU (the MI355X build has no CPU path)")
         dev = enc_states.device
         B, T = enc_states.shape[0], enc_states.shape[1]
         block = 64 if block is None else block                       # frames scored per joint call
@@ -785,6 +806,12 @@ class Transducer(nn.Module):
         n_frames = block
         key = torch.full((B,), n_frames << 32, dtype=torch.int64, device=dev)
         rows = torch.arange(n_frames, device=dev, dtype=torch.long)[None, :]
+        if details:                                                  # at most T symbols per utterance: column count[b] < T + 1
+            final_frames = torch.zeros(B, T + 1, dtype=torch.int32, device=dev)
+            final_lp = torch.zeros(B, T + 1, dtype=torch.float32, device=dev)
+            final_score = torch.zeros(B, dtype=torch.float64, device=dev)
+            frames, tok_lp, score = final_frames.clone(), final_lp.clone(), final_score.clone()
+            lp = torch.empty(B, n_frames, 2, dtype=torch.float32, device=dev)
 
         def label_states(n_hist):
             """label-encoder outputs at the last position of every history (all of length n_hist) -> [rows of the batch, 1, d]"""
@@ -800,8 +827,12 @@ class Transducer(nn.Module):
             while True:
                 idx = (t.long()[:, None] + rows).clamp_(max=T - 1)                             # frames t_b .. t_b + n_frames - 1 (beyond T_b: ignored by the scan)
                 logits = self.joint(enc_states[orig[:, None], idx], dec_state)                    # [rows, n_frames, 1, V]
-                ops.greedy_scan_batch(logits[:, :, 0, :], t, T_len, need, key)
-                ops.greedy_advance(key, n_frames, n_hist, hist, t, T_len, need, done, count, flags)
+                if details:
+                    ops.greedy_scan_batch_lp(logits[:, :, 0, :], t, T_len, need, key, lp)
+                    ops.greedy_advance_lp(key, n_frames, n_hist, hist, t, T_len, need, done, count, flags, lp, frames, tok_lp, score)
+                else:
+                    ops.greedy_scan_batch(logits[:, :, 0, :], t, T_len, need, key)
+                    ops.greedy_advance(key, n_frames, n_hist, hist, t, T_len, need, done, count, flags)
                 pending, alive = flags.tolist()                                                   # the batch's one host round trip per block
                 if pending == 0:
                     break
@@ -814,6 +845,11 @@ class Transducer(nn.Module):
                 final_hist.index_copy_(0, orig, hist)
                 final_count.index_copy_(0, orig, count)
                 keep = torch.argsort(done, stable=True)[:alive]
+                if details:
+                    final_frames.index_copy_(0, orig, frames)
+                    final_lp.index_copy_(0, orig, tok_lp)
+                    final_score.index_copy_(0, orig, score)
+                    frames, tok_lp, score, lp = frames[keep], tok_lp[keep], score[keep], lp[:alive]
                 hist, orig, t, T_len, count = hist[keep], orig[keep], t[keep].contiguous(), T_len[keep].contiguous(), count[keep].contiguous()
                 need = torch.zeros(alive, dtype=torch.int32, device=dev)
                 done = torch.zeros(alive, dtype=torch.int32, device=dev)
@@ -822,12 +858,35 @@ class Transducer(nn.Module):
             dec_state = label_states(n_hist)
         final_hist.index_copy_(0, orig, hist)
         final_count.index_copy_(0, orig, count)
+        if details:
+            final_frames.index_copy_(0, orig, frames)
+            final_lp.index_copy_(0, orig, tok_lp)
+            final_score.index_copy_(0, orig, score)
+            # ONE transfer, as f64 (exact for token ids, counts, frames and f32 log-probabilities): count | score | tokens | frames | logprobs
+            packed = torch.cat([final_count.double()[:, None], final_score[:, None], final_hist[:, 1:T + 2].double(), final_frames.double(),
+                                final_lp.double()], dim=1).cpu()
+            out = []
+            for b in range(B):
+                c = int(packed[b, 0])
+                tok, frm, lpr = (packed[b, 2 + i * (T + 1):2 + i * (T + 1) + c].tolist() for i in range(3))
+                out.append(DecodeResult([int(v) for v in tok], [int(v) for v in frm], lpr, float(packed[b, 1])))
+            return out
         final = final_hist.cpu()
         counts = final_count.cpu().tolist()
         return [final[b, 1:1 + counts[b]].tolist() for b in range(B)]
 
     @torch.no_grad()
-    def recognize(self, inputs, inputs_length=None, audio_mask=None):
+    def recognize(self, inputs, inputs_length=None, audio_mask=None, details=False):
+        """greedy recognition of a batch -> one token list per utterance; details=True -> one DecodeResult per utterance (tokens, emission
+        frames, token log-probabilities, path score), every utterance through decode_batch's device-side bookkeeping (a batch of one too;
+        with config.batched_decode = False one decode(details=True) per utterance)"""
+        if details:
+            if not inputs.is_cuda:
+                raise ValueError("recognize(details=True): inputs must live on the GPU (the MI355X build has no CPU path)")
+            enc_states = self.encoder(inputs, audio_mask)
+            if self.config.batched_decode is not False:
+                return self.decode_batch(enc_states, inputs_length, details=True)
+            return [self.decode(enc_states[b], inputs_length[b], details=True) for b in range(inputs.size(0))]
         enc_states = self.encoder(inputs, audio_mask)
         if enc_states.is_cuda and inputs.size(0) > 1 and self.config.batched_decode is not False:
             return self.decode_batch(enc_states, inputs_length)

@@ -823,3 +823,29 @@ def greedy_advance(key, n, n_hist, hist, t, T_len, need, done, count, flags):
     assert hist.dtype is torch.long and hist.stride(1) == 1
     check(lib().ttmi_greedy_advance(_p(key), c_int(B), c_int(n), c_int(n_hist), _p(hist), c_long(hist.stride(0)), _p(t), _p(T_len), _p(need),
                                     _p(done), _p(count), _p(flags), _stream()), "ttmi_greedy_advance")
+
+
+def greedy_scan_batch_lp(logits, t, T_len, need, key, lp, blank=0):
+    """greedy_scan_batch (same key) that also writes lp [B, n, 2] (f32) = log P(blank), log P(argmax) of every row it walks, from the same
+    single pass over the row (include/ttmi.h: ttmi_greedy_scan_batch_lp); rows it skips keep what lp held; device only, no synchronisation"""
+    B, n, V = logits.shape
+    _need_cuda(logits, t, T_len, need, key, lp)
+    assert lp.dtype is torch.float32 and lp.is_contiguous() and tuple(lp.shape) == (B, n, 2)
+    check(lib().ttmi_greedy_scan_batch_lp(_p(logits), c_int(_DT[logits.dtype]), c_long(logits.stride(-2)), c_int(B), c_int(n), c_int(V), c_int(blank),
+                                          _p(t), _p(T_len), _p(need), _p(key), _p(lp), _stream()), "ttmi_greedy_scan_batch_lp")
+
+
+def greedy_advance_lp(key, n, n_hist, hist, t, T_len, need, done, count, flags, lp, frames, tok_lp, score):
+    """greedy_advance (same state, same flags) that also books the block's decisions from the scan's lp (ttmi_greedy_advance_lp): frames
+    (i32) / tok_lp (f32) [B, ld_det] get the emission frame and log-probability of the symbol appended at column count[b], score (f64 [B])
+    the log-probability of the frames consumed - the greedy decoder's own path, not a path of the RNN-T lattice"""
+    B = key.shape[0]
+    _need_cuda(key, hist, lp, frames, tok_lp, score)
+    assert hist.dtype is torch.long and hist.stride(1) == 1
+    assert lp.dtype is torch.float32 and lp.is_contiguous() and tuple(lp.shape) == (B, n, 2)
+    assert frames.dtype is torch.int32 and tok_lp.dtype is torch.float32 and frames.stride(1) == 1 and tok_lp.stride(1) == 1
+    assert frames.shape[0] == B and tok_lp.shape == frames.shape and frames.stride(0) == tok_lp.stride(0)
+    assert score.dtype is torch.float64 and score.is_contiguous() and score.shape[0] == B
+    check(lib().ttmi_greedy_advance_lp(_p(key), c_int(B), c_int(n), c_int(n_hist), _p(hist), c_long(hist.stride(0)), _p(t), _p(T_len), _p(need),
+                                       _p(done), _p(count), _p(flags), _p(lp), _p(frames), _p(tok_lp), c_long(frames.stride(0)), _p(score),
+                                       _stream()), "ttmi_greedy_advance_lp")

@@ -11,6 +11,12 @@ symbol; with right_frame == 0 the kept slice `[left:-0]` is empty, so the last w
 
 Everything stays on the device: features are assembled by the front-end kernels, the encoder takes the band mask parametrically, frames
 are scored in blocks and the first emitting frame is found on the device (one host sync per emitted symbol, as in Transducer.decode).
+
+details=True: `frames` / `logprobs` grow in step with `result` (the absolute index, in the subsampled frame sequence, of the frame each symbol
+was emitted on, and log P(symbol) there) and `score` accumulates the log-probability of the greedy decisions over the frames decoded (one term per
+frame: blank's where nothing is emitted, the symbol's where one is - the decoder's own path, not a path of the RNN-T lattice; see
+tt.model.DecodeResult).  The values come from the scan's own pass over the logits (ttmi_greedy_scan_batch_lp) and ride on the one host read per
+scanned block.
 """
 import torch
 
@@ -22,7 +28,7 @@ class StreamingRecognizer:
     WIN_AUDIO, AUDIO_STEP = 15999, 15519             # samples (:53-54)
 
     def __init__(self, model, left_context=None, right_context=None, n_layer=None, n_mels=128, max_history=40, block=64,
-                 sample_rate=16000):
+                 sample_rate=16000, details=False):
         enc = model.config.enc
         self.model = model
         self.left = enc.left_context if left_context is None else left_context
@@ -31,6 +37,9 @@ class StreamingRecognizer:
         self.left_len, self.right_len = n_layer * self.left, n_layer * self.right
         self.n_mels, self.max_history, self.block, self.sr = n_mels, max_history, block, sample_rate
         self.device = next(model.parameters()).device
+        self.details = bool(details)
+        if self.details and self.device.type != "cuda":
+            raise ValueError("StreamingRecognizer(details=True): the model must live on the GPU (the MI355X build has no CPU path)")
         self.reset()
 
     def reset(self):
@@ -43,6 +52,8 @@ class StreamingRecognizer:
         self.pos = 0                                               # next frame to decode
         self.result, self.breaks, self.windows = [], [], []
         self.blank_frame = 0
+        if self.details:
+            self.frames, self.logprobs, self.score = [], [], 0.0
         with torch.no_grad():
             self.dec_state = self.model.decoder(torch.zeros(1, 1, dtype=torch.long, device=d))[:, -1:, :]      # :113-115
 
@@ -84,7 +95,11 @@ class StreamingRecognizer:
         while t < T:
             n = min(self.block, T - t)
             logits = self.model.joint(eff[t:t + n].unsqueeze(0), self.dec_state)              # [1, n, 1, V]
-            row, tok = ops.greedy_scan(logits[0, :, 0, :])
+            if self.details:
+                row, tok, lp = self._scan_lp(logits[0, :, 0, :])
+                self.score += sum(lp[2 * r] for r in range(row)) + (lp[2 * row + 1] if tok is not None else 0.0)
+            else:
+                row, tok = ops.greedy_scan(logits[0, :, 0, :])
             if self.result:
                 self.blank_frame += n if tok is None else row
             if tok is None:
@@ -96,10 +111,27 @@ class StreamingRecognizer:
                 self.breaks.append(len(self.result))
             self.result.append(tok)
             emitted.append(tok)
+            if self.details:
+                self.frames.append(self.pos + t + row)             # self.pos: the window's first frame (it moves on after the window)
+                self.logprobs.append(lp[2 * row + 1])
             hist = torch.tensor([self.result[-self.max_history:]], dtype=torch.long, device=self.device)
             self.dec_state = self.model.decoder(hist)[:, -1:, :]   # :197-203: history of at most 40 symbols, no leading blank
             self.blank_frame = 0
             t += row + 1
+
+    def _scan_lp(self, logits2d):
+        """ops.greedy_scan's (row, tok) plus the block's log-probabilities, lp[2 r] = log P(blank), lp[2 r + 1] = log P(argmax) of row r: the
+        batched scan on a batch of one, key and lp packed into ONE tensor for the block's one host read (f64 holds the key and the f32
+        values exactly)"""
+        n, dev = logits2d.shape[0], logits2d.device
+        key = torch.full((1,), n << 32, dtype=torch.int64, device=dev)
+        lp = torch.empty(1, n, 2, dtype=torch.float32, device=dev)
+        t0 = torch.zeros(1, dtype=torch.int32, device=dev)
+        ops.greedy_scan_batch_lp(logits2d[None], t0, t0 + n, t0 + 1, key, lp)      # T_len = n: every row exists; need = 1
+        packed = torch.cat([key.double(), lp.reshape(-1).double()]).tolist()
+        k = int(packed[0])
+        row, tok = k >> 32, k & 0xffffffff
+        return (row, tok, packed[1:]) if row < n else (n, None, packed[1:])
 
     @torch.no_grad()
     def feed_audio(self, samples, last=False):
