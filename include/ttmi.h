@@ -204,6 +204,34 @@ int ttmi_rnnt_align(const void* workspace /* filled by ttmi_rnnt_loss_fwd or _fw
 int ttmi_rnnt_emit_stats(const void* workspace, const int* act_lens, const int* label_lens, int B, int T, int U1,
                          float* expected, float* mass, void* stream);
 
+/* ---- CTC loss and greedy decode for an auxiliary head on the audio encoder (joint CTC - transducer training; no reference counterpart) ----
+ * logits f32 [B, T, V], batch-major, row pitch ldv >= V; labels i32 [B, U] (the tensor the RNN-T loss takes); act_lens, label_lens i32 [B],
+ * clamped as in the RNN-T loss (T_b to [1, T], U_b to [0, U]); labels clamped to [0, V-1]; U <= 1023.  For utterance b the extended sequence
+ * l' has S = 2 U_b + 1 entries, l'_{2k} = blank, l'_{2k+1} = y_k (built literally: a label equal to `blank` is not rejected), and
+ * lp(t, s) = log_softmax(z[b, t])[l'_s].
+ *     alpha(0, 0) = lp(0, 0), alpha(0, 1) = lp(0, 1), alpha(t, s) = lp(t, s) + logsumexp(alpha(t-1, s), alpha(t-1, s-1), alpha(t-1, s-2)),
+ *     the s-2 term only when l'_s != blank and l'_s != l'_{s-2};  ll = logsumexp(alpha(T_b-1, S-1), alpha(T_b-1, S-2));  costs[b] = -ll;
+ *     beta(T_b-1, S-1) = lp(T_b-1, S-1), beta(T_b-1, S-2) = lp(T_b-1, S-2), beta(t, s) = lp(t, s) + logsumexp(beta(t+1, s), beta(t+1, s+1),
+ *     beta(t+1, s+2)), the s+2 term only when l'_{s+2} != blank and l'_{s+2} != l'_s  (beta includes the emission at t).
+ * Alpha and beta are carried in fp64.  ttmi_ctc_loss_bwd, with g = scale * grad_out[b * grad_out_stride]:
+ *     d z[b, t, k] = g * ( softmax_k - sum over {s : l'_s = k} of exp(alpha(t, s) + beta(t, s) - lp(t, s) - ll) )   for t < T_b
+ * (every such row sums to zero), rows t >= T_b all zero, columns [V, ldg) zero; grad may alias logits when ldg == ldv.  The sum over the
+ * states of one symbol has one owner and a fixed order (no floating-point atomics): two runs give the same bits.  An utterance with no
+ * feasible alignment (fewer frames than labels plus adjacent repeats) has costs[b] = +inf and all-zero gradient rows, never NaN.
+ * workspace: ttmi_ctc_workspace_bytes(B, T, U) bytes, 16-byte aligned; the forward fills it (emission table, alpha, beta, ll, log-sum-exp,
+ * symbol chains), the backward reads it.  No allocation, host synchronisation or memset node: all three calls may be captured in a HIP graph.
+ * ttmi_ctc_greedy: the argmax of each of the first T_b frames, repeats collapsed, blanks dropped -> tokens[b, :count[b]] (the rest of the
+ * row is undefined).  The argmax order is the transducer scans' (NaN largest, ties to the lower index, always an index in [0, V)); if a
+ * frame's maximum is not finite (NaN, +inf, or an all -inf row) count[b] = -(1 + the first such frame) instead of a count. */
+size_t ttmi_ctc_workspace_bytes(int B, int T, int U);
+int ttmi_ctc_loss_fwd(const float* logits, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                      int B, int T, int U, int V, int blank, void* workspace, float* costs, void* stream);
+int ttmi_ctc_loss_bwd(const float* logits, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                      int B, int T, int U, int V, int blank, const void* workspace, const float* grad_out,
+                      int grad_out_stride, float scale, float* grad, long ldg, void* stream);
+int ttmi_ctc_greedy(const float* logits, long ld, const int* act_lens, int B, int T, int V, int blank,
+                    int* tokens /* [B, T] */, int* count /* [B] */, void* stream);
+
 /* ---- grouped weight gradients (data-parallel hot path): the four weight-gradient GEMMs of an encoder layer are a quarter
  * of the chip each step; deferred and launched four layers at a time they are 256 tiles, one per CU over the whole reduction - no split along
  * K, no atomics, bit-identical from run to run and across ranks.  ttmi_attn_bwd_defer / ttmi_ffn_bwd_defer are ttmi_attn_bwd / ttmi_ffn_bwd

@@ -1,0 +1,411 @@
+// CTC loss on the audio encoder's auxiliary head, and its greedy decode, for gfx950 (no reference counterpart: the reference trains the
+// transducer loss alone).
+//
+//   ctc_link_kernel       per utterance: which label positions carry the same symbol (a chain from the first occurrence through the
+//                         later ones), so that the gradient's sum over the states of one symbol has ONE owner and a fixed order.
+//   ctc_lse_kernel        HBM-bound: one wave per (b,t) row of V logits, the 16-byte online log-sum-exp walk of rnnt_lse_kernel; gathers
+//                         lp(t, s) = log_softmax(z[b,t])[l'_s] for the 2 U_b + 1 states of the extended label sequence.
+//   ctc_alphabeta_kernel  latency-bound dynamic programme: one workgroup per (utterance, direction), ONE launch for all T frames.  Thread
+//                         k owns the state pair (2k, 2k+1) = (blank before label k, label k): the s-1 neighbour of the label state is the
+//                         thread's own blank state, and the s-1 / s-2 neighbours that live elsewhere are both "label k-1", which arrives
+//                         by a one-lane DPP wave rotate (beta: the pair of thread k+1, two rotates).  U + 1 <= 64 (the training
+//                         workload's U = 50) is one wave with no barrier in the walk; longer label sequences are several waves, the
+//                         cell that crosses a wave boundary goes through a double-buffered LDS slot, one barrier per frame.  Emission
+//                         rows are prefetched CTC_PF frames ahead into registers.  Frontier in fp64 (lattice.h: lae).
+//   ctc_grad_kernel       HBM-bound: one wave per row reads the logits once and writes g * softmax once (in place allowed), then the
+//                         owners of the row's symbols overwrite their columns with g * (softmax - occupancy).  No atomics.
+//   ctc_greedy_kernel     per-frame argmax in the order of the transducer's greedy scans (rowops.h), repeats collapsed, blanks dropped.
+#include "common.h"
+#include "lattice.h"
+#include "rowops.h"
+
+namespace {
+
+using namespace ttmi_lattice;
+
+constexpr int CTC_ROW_WAVES = 4;
+constexpr int CTC_PF = 8;                 // emission rows in flight per thread of the lattice walk
+constexpr acc_t CTC_DEAD = -1e29;         // a log-likelihood below this never met a live path (dead cells sit near NEG = -1e30)
+constexpr int LINK_FIRST = 1 << 16;       // link word: bits 0..15 = next position with the same symbol + 1 (0 = none), bit 16 = first occurrence
+
+// states per frame, padded to the pairs the lattice threads own: thread k <= U holds (2k, 2k+1); state 2U+1 is padding
+__host__ __device__ __forceinline__ long ctc_sp(int U) { return 2L * (U + 1); }
+
+struct CtcWs {
+    acc_t *alpha, *beta, *ll;             // [B, T, Sp] x 2, [B]
+    float *lse, *lp;                      // [B, T], [B, T, Sp]
+    int* link;                            // [B, U]
+};
+__host__ __forceinline__ long even(long n) { return (n + 1) & ~1L; }
+CtcWs ctc_carve(void* ws, int B, int T, int U) {
+    const long n = (long)B * T * ctc_sp(U);
+    CtcWs w;
+    acc_t* q = static_cast<acc_t*>(ws);   // fp64 part first: the pairs are stored as 16-byte granules (workspace 16-byte aligned, Sp even)
+    w.alpha = q; q += n;
+    w.beta = q; q += n;
+    w.ll = q; q += even(B);
+    float* p = reinterpret_cast<float*>(q);
+    w.lse = p; p += even((long)B * T);
+    w.lp = p; p += n;
+    w.link = reinterpret_cast<int*>(p);
+    return w;
+}
+
+// ------------------------------------------------------------------ symbol chains
+__global__ __launch_bounds__(256) void ctc_link_kernel(const int* __restrict__ labels, const int* __restrict__ label_lens, int U, int V,
+                                                       int blank, int* __restrict__ link) {
+    __shared__ int y[1024];
+    const int b = blockIdx.x;
+    const int Ub = clampi(label_lens[b], 0, U);
+    for (int u = threadIdx.x; u < Ub; u += 256) y[u] = clampi(labels[(long)b * U + u], 0, V - 1);
+    __syncthreads();
+    for (int u = threadIdx.x; u < Ub; u += 256) {
+        int w = 0;
+        if (y[u] != blank) {               // a label equal to `blank` is one more blank state: the blank column's owner (lane 0) sums it
+            bool first = true;
+            for (int j = 0; j < u; ++j) first = first && (y[j] != y[u]);
+            int nxt = -1;
+            for (int j = Ub - 1; j > u; --j) nxt = (y[j] == y[u]) ? j : nxt;
+            w = (nxt + 1) | (first ? LINK_FIRST : 0);
+        }
+        link[(long)b * U + u] = w;
+    }
+}
+
+// ------------------------------------------------------------------ lse + gather
+__global__ __launch_bounds__(CTC_ROW_WAVES * 64) void ctc_lse_kernel(
+    const float* __restrict__ logits, long ldv, const int* __restrict__ labels, const int* __restrict__ act_lens,
+    const int* __restrict__ label_lens, int B, int T, int U, int V, int blank, int vec_ok, float* __restrict__ lse,
+    float* __restrict__ lp) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * CTC_ROW_WAVES + (threadIdx.x >> 6);
+    if (row >= (long)B * T) return;
+    const int t = (int)(row % T);
+    const int b = (int)(row / T);
+    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U);
+    if (t >= Tb) return;
+    const float* r = logits + row * ldv;
+    float m = NEG, s = 0.f;
+    auto upd = [&](float x) {
+        const float mn = fmaxf(m, x);
+        s = s * __expf(m - mn) + __expf(x - mn);
+        m = mn;
+    };
+    const int head = row_head<float>(r, V, vec_ok);
+    for (int i = lane; i < head; i += 64) upd(r[i]);
+    const int nvec = (V - head) / 4;
+    for (int i = lane; i < nvec; i += 64) {
+        Vec16<float> x;
+        x.template load<false>(r + head + i * 4);
+        const float mx = fmaxf(fmaxf(x.f[0], x.f[1]), fmaxf(x.f[2], x.f[3]));
+        const float mn = fmaxf(m, mx);
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc += __expf(x.f[k] - mn);
+        s = s * __expf(m - mn) + acc;
+        m = mn;
+    }
+    for (int i = head + nvec * 4 + lane; i < V; i += 64) upd(r[i]);
+    const float M = wave_max(m);
+    s = wave_sum(s * __expf(m - M));
+    const float l = M + __logf(s);
+    if (lane == 0) lse[row] = l;
+    // the row's 2 U_b + 1 emission log-probs (the row is in cache: it has just been read); clamped at NEG so that a -inf logit is a dead
+    // transition and not an inf - inf in the log-add-exp (a NaN stays a NaN)
+    float* lpr = lp + row * ctc_sp(U);
+    const int S = 2 * Ub + 1;
+    for (int si = lane; si < S; si += 64) {
+        const int sym = (si & 1) ? clampi(labels[(long)b * U + (si >> 1)], 0, V - 1) : blank;
+        const float v = r[sym] - l;
+        lpr[si] = v < NEG ? NEG : v;
+    }
+}
+
+// ------------------------------------------------------------------ alpha / beta
+template <bool MULTI>
+__global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_alphabeta_kernel(
+    const float* __restrict__ lp, const int* __restrict__ labels, const int* __restrict__ act_lens, const int* __restrict__ label_lens,
+    int T, int U, int V, int blank, acc_t* __restrict__ alpha, acc_t* __restrict__ beta, acc_t* __restrict__ ll,
+    float* __restrict__ costs) {
+    __shared__ acc_t bnd[2][16][2];       // the cells that cross a wave boundary, double-buffered by frame parity
+    __shared__ acc_t fin;
+    const int b = blockIdx.x >> 1;
+    const bool do_beta = blockIdx.x & 1;
+    const int k = threadIdx.x, lane = k & 63, wave = k >> 6, W = blockDim.x >> 6;
+    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U);
+    const bool vb = k <= Ub, vl = k < Ub;             // this thread's blank / label state exists
+    const int* lab = labels + (long)b * U;
+    const int yk = vl ? clampi(lab[k], 0, V - 1) : -1;
+    const long rp = ctc_sp(U) / 2;                    // pairs per frame
+    const int kc = k <= U ? k : U;                    // in-range pair for the (unconditional) loads of the threads that pad the last wave
+    const float2* e2 = reinterpret_cast<const float2*>(lp + (long)b * T * ctc_sp(U)) + kc;
+    double2* out = reinterpret_cast<double2*>((do_beta ? beta : alpha) + (long)b * T * ctc_sp(U)) + kc;
+    const bool wr = k <= U;
+    float2 cur[CTC_PF], nxt[CTC_PF];
+    if (!do_beta) {
+        // skip transition into label state 2k+1 from 2k-1: l'_s != blank and l'_s != l'_{s-2}
+        const bool skip = vl && k > 0 && yk != blank && yk != clampi(lab[k > 0 ? k - 1 : 0], 0, V - 1);
+        const float2 e0 = e2[0];
+        acc_t ab = k == 0 ? (acc_t)e0.x : (acc_t)NEG;
+        acc_t al = (k == 0 && vl) ? (acc_t)e0.y : (acc_t)NEG;
+        if (wr) out[0] = make_double2(ab, al);
+#pragma unroll
+        for (int i = 0; i < CTC_PF; ++i) cur[i] = e2[(long)min(1 + i, Tb - 1) * rp];
+        for (int base = 1; base < Tb; base += CTC_PF) {
+#pragma unroll
+            for (int i = 0; i < CTC_PF; ++i) nxt[i] = e2[(long)min(base + CTC_PF + i, Tb - 1) * rp];
+#pragma unroll
+            for (int i = 0; i < CTC_PF; ++i) {
+                const int t = base + i;
+                if (t < Tb) {                          // workgroup-uniform
+                    if (MULTI) {
+                        if (lane == 63) bnd[t & 1][wave][0] = al;
+                        __syncthreads();
+                    }
+                    acc_t nb = rot_r1(al);             // label state of thread k-1 at frame t-1
+                    if (lane == 0) nb = (MULTI && wave > 0) ? bnd[t & 1][wave > 0 ? wave - 1 : 0][0] : (acc_t)NEG;
+                    acc_t ml = lae(al, ab);
+                    if (skip) ml = lae(ml, nb);
+                    const acc_t nab = vb ? (acc_t)cur[i].x + lae(ab, nb) : (acc_t)NEG;
+                    al = vl ? (acc_t)cur[i].y + ml : (acc_t)NEG;
+                    ab = nab;
+                    if (wr) out[(long)t * rp] = make_double2(ab, al);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < CTC_PF; ++i) cur[i] = nxt[i];
+        }
+        // ll = logsumexp(alpha(T_b-1, 2 U_b), alpha(T_b-1, 2 U_b - 1)): thread U_b holds the first, thread U_b - 1 the second
+        if (Ub > 0 && k == Ub - 1) fin = al;
+        __syncthreads();
+        if (k == Ub) {
+            const acc_t v = Ub > 0 ? lae(ab, fin) : ab;
+            ll[b] = v;
+            costs[b] = v <= CTC_DEAD ? INFINITY : (float)(-v);      // no feasible alignment: +inf (a NaN stays a NaN)
+        }
+    } else {
+        // skip transition out of label state 2k+1 into 2k+3: l'_{s+2} != blank and l'_{s+2} != l'_s
+        const int yn = (k + 1 < Ub) ? clampi(lab[k + 1 < Ub ? k + 1 : 0], 0, V - 1) : -1;
+        const bool skip = (k + 1 < Ub) && yn != blank && yn != yk;
+        const float2 e0 = e2[(long)(Tb - 1) * rp];
+        acc_t bb = k == Ub ? (acc_t)e0.x : (acc_t)NEG;
+        acc_t bl = k == Ub - 1 ? (acc_t)e0.y : (acc_t)NEG;
+        if (wr) out[(long)(Tb - 1) * rp] = make_double2(bb, bl);
+#pragma unroll
+        for (int i = 0; i < CTC_PF; ++i) cur[i] = e2[(long)max(Tb - 2 - i, 0) * rp];
+        for (int base = Tb - 2; base >= 0; base -= CTC_PF) {
+#pragma unroll
+            for (int i = 0; i < CTC_PF; ++i) nxt[i] = e2[(long)max(base - CTC_PF - i, 0) * rp];
+#pragma unroll
+            for (int i = 0; i < CTC_PF; ++i) {
+                const int t = base - i;
+                if (t >= 0) {                          // workgroup-uniform
+                    if (MULTI) {
+                        if (lane == 0) { bnd[t & 1][wave][0] = bb; bnd[t & 1][wave][1] = bl; }
+                        __syncthreads();
+                    }
+                    acc_t nbb = rot_l1(bb), nbl = rot_l1(bl);          // the pair of thread k+1 at frame t+1
+                    if (lane == 63) {
+                        const bool has = MULTI && wave + 1 < W;
+                        nbb = has ? bnd[t & 1][wave + 1 < W ? wave + 1 : wave][0] : (acc_t)NEG;
+                        nbl = has ? bnd[t & 1][wave + 1 < W ? wave + 1 : wave][1] : (acc_t)NEG;
+                    }
+                    acc_t ml = lae(bl, nbb);
+                    if (skip) ml = lae(ml, nbl);
+                    const acc_t nbbv = vb ? (acc_t)cur[i].x + lae(bb, bl) : (acc_t)NEG;
+                    bl = vl ? (acc_t)cur[i].y + ml : (acc_t)NEG;
+                    bb = nbbv;
+                    if (wr) out[(long)t * rp] = make_double2(bb, bl);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < CTC_PF; ++i) cur[i] = nxt[i];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ gradient
+__global__ __launch_bounds__(CTC_ROW_WAVES * 64) void ctc_grad_kernel(
+    const float* logits, long ldv, const int* __restrict__ labels, const int* __restrict__ act_lens, const int* __restrict__ label_lens,
+    int B, int T, int U, int V, int blank, int vec_ok, const float* __restrict__ lse, const float* __restrict__ lp,
+    const acc_t* __restrict__ alpha, const acc_t* __restrict__ beta, const acc_t* __restrict__ ll, const int* __restrict__ link,
+    const float* __restrict__ grad_out, int grad_out_stride, float scale, float* grad, long ldg) {
+    const int lane = threadIdx.x & 63;
+    const long row = (long)blockIdx.x * CTC_ROW_WAVES + (threadIdx.x >> 6);
+    if (row >= (long)B * T) return;
+    const int t = (int)(row % T);
+    const int b = (int)(row / T);
+    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U);
+    const acc_t L = ll[b];
+    const bool live = (t < Tb) && (L > CTC_DEAD);      // frames past the utterance and utterances without a feasible alignment: zero rows
+    const float* r = logits + row * ldv;
+    float* g = grad + row * ldg;
+    float l = 0.f, gs = 0.f;
+    if (live) {
+        l = lse[row];
+        gs = scale * grad_out[(long)b * grad_out_stride];
+    }
+    auto f = [&](float x) -> float { return live ? gs * __expf(x - l) : 0.f; };
+    const int head = row_head<float>(r, V, vec_ok);
+    for (int i = lane; i < head; i += 64) g[i] = f(live ? r[i] : 0.f);
+    const int nvec = (V - head) / 4;
+    for (int i = lane; i < nvec; i += 64) {
+        Vec16<float> x;
+        const int v0 = head + i * 4;
+        if (live) x.load(r + v0);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) x.f[k] = f(live ? x.f[k] : 0.f);
+        x.store(g + v0);
+    }
+    for (int i = head + nvec * 4 + lane; i < V; i += 64) g[i] = f(live ? r[i] : 0.f);
+    for (int i = V + lane; i < ldg; i += 64) g[i] = 0.f;      // padded pitch: the head's dgrad / wgrad GEMMs may run over the full pitch
+    if (!live) return;                                          // (wave-uniform)
+    // the columns of the row's own symbols: g * (softmax - sum over the states of that symbol of exp(alpha + beta - lp - ll)).  The wave's
+    // softmax stores above are complete before these overwrite them; each column has ONE owner lane that adds its states in label order.
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    const long Sp = ctc_sp(U);
+    const double2* a2 = reinterpret_cast<const double2*>(alpha + row * Sp);
+    const double2* b2 = reinterpret_cast<const double2*>(beta + row * Sp);
+    const float2* e2 = reinterpret_cast<const float2*>(lp + row * Sp);
+    const int* lk = link + (long)b * U;
+    const int* lab = labels + (long)b * U;
+    auto occ = [&](acc_t a, acc_t bt, float e) -> float { return __expf((float)(a + bt - L - (acc_t)e)); };
+    float accb = 0.f;
+    for (int k = lane; k <= Ub; k += 64) {
+        const double2 a = a2[k], be = b2[k];
+        const float2 e = e2[k];
+        accb += occ(a.x, be.x, e.x);
+        if (k < Ub) {
+            const int w = lk[k];
+            const int y = clampi(lab[k], 0, V - 1);
+            if (y == blank) {
+                accb += occ(a.y, be.y, e.y);
+            } else if (w & LINK_FIRST) {
+                float sum = occ(a.y, be.y, e.y);
+                for (int j = (w & 0xffff) - 1; j >= 0; j = (lk[j] & 0xffff) - 1) sum += occ(a2[j].y, b2[j].y, e2[j].y);
+                g[y] = gs * (__expf(e.y) - sum);
+            }
+        }
+    }
+    const float tot = wave_sum(accb);
+    if (lane == 0) g[blank] = gs * (__expf(e2[0].x) - tot);
+}
+
+// ------------------------------------------------------------------ greedy decode
+// One workgroup per utterance.  Its waves take the frames' argmax (tokens[b, t] holds frame t's symbol for a moment), then wave 0 compacts
+// the row in place, 64 frames at a time: keep frame t iff its symbol is not blank and differs from frame t-1's.  A kept frame lands at an
+// index <= t, and only a frame's own value is ever written at its own index, so the symbols still to be read are intact.
+// A frame without a finite maximum (NaN, +inf, or all -inf) gets the symbol the greedy scans give it (rowops.h) and is reported through
+// count[b] = -(1 + first such frame).
+__global__ __launch_bounds__(256) void ctc_greedy_kernel(const float* __restrict__ logits, long ld, const int* __restrict__ act_lens, int T,
+                                                         int V, int blank, int* __restrict__ tokens, int* __restrict__ count) {
+    __shared__ int bad;
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int Tb = clampi(act_lens[b], 1, T);
+    int* tok = tokens + (long)b * T;
+    if (threadIdx.x == 0) bad = 0x7fffffff;
+    __syncthreads();
+    for (int t = wave; t < Tb; t += 4) {
+        const float* r = logits + ((long)b * T + t) * ld;
+        const int bi = wave_row_argmax(r, V, lane);
+        if (lane == 0) {
+            tok[t] = bi;
+            const float x = r[bi];
+            if (!(fabsf(x) < INFINITY)) atomicMin(&bad, t);
+        }
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    int n = 0, last = -1;                               // tokens kept so far; symbol of the frame before this chunk
+    for (int base = 0; base < Tb; base += 64) {
+        const int t = base + lane;
+        const int a = t < Tb ? tok[t] : blank;
+        int prev = __shfl_up(a, 1, 64);
+        if (lane == 0) prev = last;
+        const bool keep = t < Tb && a != blank && a != prev;
+        const unsigned long long mask = __ballot(keep);
+        __builtin_amdgcn_wave_barrier();                // every lane has read its frame before any lane writes
+        if (keep) tok[n + __popcll(mask & ((1ull << lane) - 1ull))] = a;
+        n += __popcll(mask);
+        last = __shfl(a, 63, 64);
+    }
+    if (lane == 0) count[b] = bad != 0x7fffffff ? -(1 + bad) : n;
+}
+
+}  // namespace
+
+extern "C" {
+
+// bytes of caller-provided workspace shared by ttmi_ctc_loss_fwd / _bwd (16-byte aligned): lp table, alpha, beta, ll, lse, symbol chains
+size_t ttmi_ctc_workspace_bytes(int B, int T, int U) {
+    if (B <= 0 || T <= 0 || U < 0) return 0;
+    const size_t n = (size_t)B * T * ctc_sp(U);
+    return sizeof(acc_t) * (2 * n + even(B)) + sizeof(float) * (even((long)B * T) + n) + sizeof(int) * ((size_t)B * (U > 0 ? U : 1)) + 64;
+}
+
+int ttmi_ctc_loss_fwd(const float* logits, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U,
+                      int V, int blank, void* workspace, float* costs, void* stream) {
+    TTMI_REQUIRE(logits && (labels || U == 0) && act_lens && label_lens && workspace && costs, "ctc_loss_fwd: null pointer");
+    TTMI_REQUIRE(B > 0 && T > 0 && U >= 0 && V > 0, "ctc_loss_fwd: bad shape B=%d T=%d U=%d V=%d", B, T, U, V);
+    TTMI_REQUIRE(ldv >= V, "ctc_loss_fwd: bad pitch");
+    TTMI_REQUIRE(blank >= 0 && blank < V, "ctc_loss_fwd: blank %d outside [0,%d)", blank, V);
+    TTMI_REQUIRE(U <= 1023, "ctc_loss_fwd: U=%d > 1023 unsupported", U);
+    TTMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ctc_loss_fwd: workspace must be 16-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CtcWs w = ctc_carve(workspace, B, T, U);
+    const long rows = (long)B * T;
+    const int vec_ok = ((reinterpret_cast<uintptr_t>(logits) % 4) == 0) ? 1 : 0;
+    if (U > 0) {
+        hipLaunchKernelGGL(ctc_link_kernel, dim3(B), dim3(256), 0, st, labels, label_lens, U, V, blank, w.link);
+        TTMI_LAUNCH_CHECK("ctc_link_kernel");
+    }
+    hipLaunchKernelGGL(ctc_lse_kernel, dim3(cdiv(rows, CTC_ROW_WAVES)), dim3(CTC_ROW_WAVES * 64), 0, st, logits, ldv, labels, act_lens,
+                       label_lens, B, T, U, V, blank, vec_ok, w.lse, w.lp);
+    TTMI_LAUNCH_CHECK("ctc_lse_kernel");
+    const int threads = cdiv(U + 1, 64) * 64;
+    if (threads == 64)
+        hipLaunchKernelGGL(ctc_alphabeta_kernel<false>, dim3(2 * B), dim3(64), 0, st, w.lp, labels, act_lens, label_lens, T, U, V, blank,
+                           w.alpha, w.beta, w.ll, costs);
+    else
+        hipLaunchKernelGGL(ctc_alphabeta_kernel<true>, dim3(2 * B), dim3(threads), 0, st, w.lp, labels, act_lens, label_lens, T, U, V, blank,
+                           w.alpha, w.beta, w.ll, costs);
+    TTMI_LAUNCH_CHECK("ctc_alphabeta_kernel");
+    return TTMI_OK;
+}
+
+int ttmi_ctc_loss_bwd(const float* logits, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U,
+                      int V, int blank, const void* workspace, const float* grad_out, int grad_out_stride, float scale, float* grad,
+                      long ldg, void* stream) {
+    TTMI_REQUIRE(logits && (labels || U == 0) && act_lens && label_lens && workspace && grad_out && grad, "ctc_loss_bwd: null pointer");
+    TTMI_REQUIRE(B > 0 && T > 0 && U >= 0 && V > 0, "ctc_loss_bwd: bad shape B=%d T=%d U=%d V=%d", B, T, U, V);
+    TTMI_REQUIRE(ldv >= V && ldg >= V, "ctc_loss_bwd: bad pitch");
+    TTMI_REQUIRE(blank >= 0 && blank < V, "ctc_loss_bwd: blank %d outside [0,%d)", blank, V);
+    TTMI_REQUIRE(U <= 1023, "ctc_loss_bwd: U=%d > 1023 unsupported", U);
+    TTMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ctc_loss_bwd: workspace must be 16-byte aligned");
+    TTMI_REQUIRE(static_cast<const void*>(logits) != static_cast<const void*>(grad) || ldg == ldv, "ctc_loss_bwd: in-place needs ldg == ldv");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    CtcWs w = ctc_carve(const_cast<void*>(workspace), B, T, U);
+    const long rows = (long)B * T;
+    // vector path needs logits and grad rows to share their 16-byte phase
+    const int vec_ok = ((reinterpret_cast<uintptr_t>(logits) % 16) == (reinterpret_cast<uintptr_t>(grad) % 16) && ((ldv - ldg) * 4L) % 16 == 0 &&
+                        (reinterpret_cast<uintptr_t>(logits) % 4) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(ctc_grad_kernel, dim3(cdiv(rows, CTC_ROW_WAVES)), dim3(CTC_ROW_WAVES * 64), 0, st, logits, ldv, labels, act_lens,
+                       label_lens, B, T, U, V, blank, vec_ok, w.lse, w.lp, w.alpha, w.beta, w.ll, w.link, grad_out, grad_out_stride, scale,
+                       grad, ldg);
+    TTMI_LAUNCH_CHECK("ctc_grad_kernel");
+    return TTMI_OK;
+}
+
+int ttmi_ctc_greedy(const float* logits, long ld, const int* act_lens, int B, int T, int V, int blank, int* tokens, int* count,
+                    void* stream) {
+    TTMI_REQUIRE(logits && act_lens && tokens && count, "ctc_greedy: null pointer");
+    TTMI_REQUIRE(B > 0 && T > 0 && V > 0 && ld >= V, "ctc_greedy: bad shape B=%d T=%d V=%d ld=%ld", B, T, V, ld);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B), dim3(256), 0, st, logits, ld, act_lens, T, V, blank, tokens, count);
+    TTMI_LAUNCH_CHECK("ctc_greedy_kernel");
+    return TTMI_OK;
+}
+
+}  // extern "C"

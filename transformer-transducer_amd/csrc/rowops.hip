@@ -1459,34 +1459,7 @@ __global__ __launch_bounds__(256) void transpose_batched_kernel(const TS* __rest
     }
 }
 
-// argmax order of the greedy scans = torch.argmax's: NaN is larger than every number, equal values (and NaN against NaN) go to the lower
-// index.  A lane starts from (-inf, 0x7fffffff), which loses to every real entry - to -inf too, by its index - so a row of V >= 1 entries
-// always ends on an index in [0, V): an all -inf row on 0, a row with NaN on its first NaN.
-__device__ __forceinline__ bool argmax_takes(float x, int xi, float best, int bi) {
-    const bool xn = x != x, bn = best != best;
-    return (x > best) | (xn & !bn) | (((x == best) | (xn & bn)) & (xi < bi));
-}
-
-// one wave, one row: every lane returns the row's argmax in that order
-template <typename TL>
-__device__ __forceinline__ int wave_row_argmax(const TL* __restrict__ r, int V, int lane) {
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int v = lane; v < V; v += 64) {
-        float x;
-        if constexpr (sizeof(TL) == 4) x = r[v];
-        else x = bf16_to_f32(r[v]);
-        if (argmax_takes(x, v, best, bi)) { best = x; bi = v; }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (argmax_takes(ob, oi, best, bi)) { best = ob; bi = oi; }
-    }
-    return bi;
-}
-
+// (the argmax order of the greedy scans, argmax_takes / wave_row_argmax, lives in rowops.h: ctc.hip decodes by the same rule)
 // greedy scan: rows of logits (f32 or bf16, pitch ld); out[0] = first row whose argmax != blank (or n), out[1] = that argmax.
 // One wave per row computes the argmax (first maximal index, like torch.argmax, rows without a finite maximum included); the rows' results
 // go through a single atomicMin on the packed (row << 32 | token) key, so one 8-byte D2H read tells the host where the next symbol is.

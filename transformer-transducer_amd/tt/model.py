@@ -207,6 +207,59 @@ class _JointLossFn(torch.autograd.Function):
         return (denc * gout, ddec * gout, *rets, None, None, None, None, None, None, None, None, None, None)
 
 
+class _CTCHeadLossFn(torch.autograd.Function):
+    """auxiliary CTC head on the audio encoder's output + CTC loss as ONE op, in the manner of _JointLossFn: the [B, T, V] logits live in a
+    row-padded buffer (ops.padded_empty) that the loss gradient overwrites in place (ttmi_ctc_loss_bwd) and the head's dgrad / wgrad /
+    bias-sum products consume in the forward pass; backward() only scales by the incoming gradient.  Every product is the library's own
+    GEMM (ops.linear_*): bf16 MFMA with f32 output in the bf16 mode, the exact-f32 / three-term paths in the fp32 / bf16x3 modes."""
+
+    @staticmethod
+    def forward(ctx, enc, w, b, labels, act_lens, label_lens, prec, reduction, grad_mode=True, blank=0):
+        enc = enc.contiguous()
+        B, T, d = enc.shape
+        V = w.shape[0]
+        w_, b_ = w.detach(), b.detach()
+        x2 = enc.detach().reshape(B * T, d)
+        buf, logits = ops.padded_empty((B, T, V), torch.float32, enc.device)
+        l2 = buf.view(B * T, buf.shape[-1])[:, :V]
+        ops.linear_nt(x2, w_, l2, bias=b_, prec=prec)
+        ws = ops.ctc_workspace(B, T, labels.shape[1], enc.device)
+        costs = ops.ctc_loss_fwd(logits, labels, act_lens, label_lens, blank, ws)
+        need = grad_mode and any(ctx.needs_input_grad[:3])
+        scale = 1.0 / B if reduction == "mean" else 1.0
+        if need:
+            one = torch.ones(1, dtype=torch.float32, device=enc.device)
+            ops.ctc_loss_bwd(logits, labels, act_lens, label_lens, blank, ws, one, 0, scale, inplace=True)      # l2 now holds d loss / d logits
+            denc, gw, gb = torch.empty_like(enc), torch.empty_like(w_), torch.empty_like(b_)
+            ops.linear_nn(l2, w_, denc.view(B * T, d), prec=prec)
+            ops.linear_tn(l2, x2, gw, prec=prec, accumulate=False)
+            ops.linear_tn(l2, torch.ones(B * T, 1, dtype=torch.float32, device=enc.device), gb, prec=prec, accumulate=False)
+            ctx.save_for_backward(denc, gw, gb)
+        ctx.params = (w, b)
+        if reduction == "none":
+            return costs
+        return costs.sum().reshape(1) * scale
+
+    @staticmethod
+    def backward(ctx, gout):
+        denc, *gs = ctx.saved_tensors
+        gout = gout.float()
+        if gout.numel() != 1:
+            raise NotImplementedError("fused CTC head + loss: per-utterance upstream gradients (reduction='none') are not supported; "
+                                      "use model.ctc_head(enc_state) + ttmi.ctc.ctc_loss(reduction='none')")
+        rets = []
+        for prm, gp in zip(ctx.params, gs):
+            if getattr(prm, "_ttmi_direct", False) and prm.grad is not None:       # FlatModel: accumulate into the flat gradient buffer
+                prm.grad.addcmul_(gp, gout)
+                rets.append(None)
+                cb = getattr(prm, "_ttmi_on_grad", None)
+                if cb is not None:
+                    cb()
+            else:
+                rets.append(gp * gout)
+        return (denc * gout, *rets, None, None, None, None, None, None, None)
+
+
 def _joint_align(joint, enc, dec, labels, act_lens, label_lens, prec, chunk, blank, exp_state, stats):
     """joint network + loss forward + forced alignment, forward only, chunked over utterances as _JointLossFn.forward chunks: per chunk
     ttmi_joint_fwd + ttmi_rnnt_loss_fwd + ttmi_rnnt_align (+ ttmi_rnnt_emit_stats), or, with `exp_state` (the JointNet's _ExpShift) valid
@@ -561,19 +614,29 @@ class Transducer(nn.Module):
         if config.share_embedding:
             # the reference's branch dereferences self.decoder.embedding, which does not exist (tt/model.py:53-56)
             raise AttributeError("'BuildDecoder' object has no attribute 'embedding' (share_embedding is broken upstream)")
+        # optional auxiliary CTC head on the audio encoder's output (joint CTC - transducer training; config.ctc_weight absent, None or 0:
+        # no head, the module and its state_dict are the reference's)
+        self.ctc_weight = float(config.ctc_weight or 0.0)
+        if self.ctc_weight < 0.0:
+            raise ValueError("config.ctc_weight must be >= 0, got %r" % (config.ctc_weight,))
+        if self.ctc_weight > 0.0:
+            self.ctc_head = nn.Linear(config.enc.d_model, config.vocab_size)
 
     def forward(self, inputs, targets):
         """-> logits [B, T, U+1, V] (tt/model.py:58-68).  In the bf16 pipeline the return value is a DeferredLogits handle on the two
         encoder states: `RNNTLoss` (train.py:53) consumes it through the fused joint + loss kernels, anything else makes it produce
         the real logits first - train.py:51-53 runs unchanged and on the fast path (deferred_logits_enabled for the switches)."""
         enc_state, dec_state = self._encode(inputs, targets)
+        if self.ctc_weight > 0.0:
+            # the two-call form (train.py:51-53) reaches the head's input through here: ctc_loss_from_last_forward() consumes and releases it
+            self.__dict__["_ctc_states"] = enc_state
         prec = default_precision()
         if enc_state.is_cuda and deferred_logits_enabled(self.config, prec):
             return DeferredLogits(self.joint, enc_state, dec_state, prec)
         return self.joint(enc_state, dec_state)
 
     def loss(self, inputs, inputs_length, targets, targets_length, reduction="mean", chunk=None, check_lengths=True, exp_domain=False, *,
-             fastemit_lambda=0.0):
+             fastemit_lambda=0.0, ctc_weight=None):
         """Opt-in fused form of train.py:51-53 (`logits = model(inputs, targets); loss = criterion(logits, targets.int(),
         inputs_length.int(), targets_length.int())`) that never materialises the logits (API precedent: tt_espnet/model.py:35-81 returns
         the loss from forward).  Same numbers as the two-call form: the same kernels run, one chunk of `chunk` utterances at a time
@@ -586,9 +649,13 @@ class Transducer(nn.Module):
         call on a module (and the first after its joint weights were replaced) runs the form above and seeds the shift on the device
         (_ExpShift): no host synchronisation.
 
-        fastemit_lambda: FastEmit regularisation of the gradient, as in warprnnt_pytorch.RNNTLoss (the loss value is unchanged)."""
+        fastemit_lambda: FastEmit regularisation of the gradient, as in warprnnt_pytorch.RNNTLoss (the loss value is unchanged).
+
+        ctc_weight (None: config.ctc_weight): > 0 returns rnnt + ctc_weight * ctc, the CTC loss of the auxiliary head (`ctc_head`, built when
+        config.ctc_weight > 0) on the same audio-encoder states - the encoder runs once.  ValueError on a module without the head."""
         from warprnnt_pytorch import check_lengths as certify
         fastemit_lambda = ops.check_fastemit(fastemit_lambda)
+        ctc_weight = self._ctc_weight(ctc_weight)
         enc_state, dec_state = self._encode(inputs, targets)
         B, T, U1 = enc_state.shape[0], enc_state.shape[1], dec_state.shape[1]
         labels, al, ll = (t.to(device=enc_state.device, dtype=torch.int32).contiguous() for t in (targets, inputs_length, targets_length))
@@ -598,10 +665,72 @@ class Transducer(nn.Module):
         if chunk is None:
             chunk = self.default_loss_chunk(B, T, U1, exp_domain)
         j = self.joint
-        return _JointLossFn.apply(enc_state, dec_state, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
+        rnnt = _JointLossFn.apply(enc_state, dec_state, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
                                   j.project_layer.bias, labels, al, ll, prec, int(chunk), reduction,
                                   j.exp_shift_state(enc_state.device) if exp_domain and prec == 1 else None, torch.is_grad_enabled(), 0,
                                   fastemit_lambda)
+        if ctc_weight > 0.0:
+            return rnnt + ctc_weight * self._ctc_from_states(enc_state, labels, al, ll, reduction)
+        return rnnt
+
+    def _ctc_weight(self, ctc_weight):
+        """the weight a call uses: None -> the config's; ValueError for a negative one, or a positive one on a module without the head"""
+        w = self.ctc_weight if ctc_weight is None else float(ctc_weight)
+        if not w >= 0.0:
+            raise ValueError("ctc_weight must be >= 0, got %r" % (ctc_weight,))
+        if w > 0.0 and getattr(self, "ctc_head", None) is None:
+            raise ValueError("ctc_weight = %g on a Transducer without a CTC head: build it with config.ctc_weight > 0" % w)
+        return w
+
+    def _ctc_from_states(self, enc_state, labels, act_lens, label_lens, reduction):
+        """CTC loss of the head on audio-encoder states [B, T, d] (head projection, loss and their backward as one op: _CTCHeadLossFn)"""
+        if getattr(self, "ctc_head", None) is None:
+            raise ValueError("this Transducer has no CTC head: build it with config.ctc_weight > 0")
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("reduction must be 'mean', 'sum' or 'none'")
+        if not enc_state.is_cuda:
+            raise ValueError("Transducer.ctc_loss: inputs must live on the GPU (the MI355X build has no CPU path)")
+        labels, act_lens, label_lens = (t.to(device=enc_state.device, dtype=torch.int32).contiguous() for t in (labels, act_lens, label_lens))
+        ops.weights_fresh()
+        return _CTCHeadLossFn.apply(enc_state, self.ctc_head.weight, self.ctc_head.bias, labels, act_lens, label_lens, default_precision(),
+                                    reduction, torch.is_grad_enabled(), 0)
+
+    def ctc_loss(self, inputs, inputs_length, targets, targets_length, reduction="mean"):
+        """CTC loss of the auxiliary head alone (blank = 0, the transducer's): the audio encoder, the head and ttmi.ctc's kernels.
+        reduction as in `loss` ('mean' divides by the batch size).  ValueError on a module without the head."""
+        if getattr(self, "ctc_head", None) is None:
+            raise ValueError("this Transducer has no CTC head: build it with config.ctc_weight > 0")
+        if not inputs.is_cuda:
+            raise ValueError("Transducer.ctc_loss: inputs must live on the GPU (the MI355X build has no CPU path)")
+        enc_state = self.encoder(inputs, self._audio_mask(inputs))
+        return self._ctc_from_states(enc_state, targets, inputs_length, targets_length, reduction)
+
+    def ctc_loss_from_last_forward(self, targets, inputs_length, targets_length, reduction="mean"):
+        """the head's CTC loss on the audio states the last `forward` kept, for the two-call form `logits = model(x, y); loss =
+        criterion(logits, ...)` (train.py:51-53; ttmi.dp_train wraps the criterion with it).  The reference is released here."""
+        enc_state = self.__dict__.pop("_ctc_states", None)
+        if enc_state is None:
+            raise RuntimeError("ctc_loss_from_last_forward: no audio states kept (call the model first; one loss per forward)")
+        return self._ctc_from_states(enc_state, targets, inputs_length, targets_length, reduction)
+
+    @torch.no_grad()
+    def recognize_ctc(self, inputs, inputs_length=None, audio_mask=None):
+        """non-autoregressive recognition with the CTC head: per utterance the argmax of the head over its frames, repeats collapsed, blanks
+        dropped (ttmi.ctc.ctc_greedy_decode) -> one token list per utterance"""
+        from ttmi.ctc import ctc_greedy_decode
+        if getattr(self, "ctc_head", None) is None:
+            raise ValueError("this Transducer has no CTC head: build it with config.ctc_weight > 0")
+        if not inputs.is_cuda:
+            raise ValueError("recognize_ctc: inputs must live on the GPU (the MI355X build has no CPU path)")
+        enc_state = self.encoder(inputs, self._audio_mask(inputs) if audio_mask is None else audio_mask).contiguous()
+        B, T, d = enc_state.shape
+        V = self.ctc_head.out_features
+        buf, logits = ops.padded_empty((B, T, V), torch.float32, enc_state.device)
+        ops.weights_fresh()
+        ops.linear_nt(enc_state.reshape(B * T, d), self.ctc_head.weight.detach(), buf.view(B * T, buf.shape[-1])[:, :V],
+                      bias=self.ctc_head.bias.detach(), prec=default_precision())
+        lens = None if inputs_length is None else torch.as_tensor(inputs_length).to(enc_state.device)
+        return ctc_greedy_decode(logits, lens, blank=0)
 
     def align(self, inputs, inputs_length, targets, targets_length, chunk=None, check_lengths=True, exp_domain=False, *, stats=False):
         """Forced alignment of `targets` to `inputs`: the best path through the RNN-T lattice, without materialising the logits (the chunked

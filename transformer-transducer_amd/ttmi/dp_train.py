@@ -68,6 +68,28 @@ def wrap_for_data_parallel(model, optimizer, bucket_mb=32):
     return DataParallelOptimizer(optimizer, sync), sync
 
 
+class CTCAugmentedCriterion:
+    """the `criterion` train.py's loop sees when `training.ctc_weight` > 0: `criterion(logits, targets, inputs_length, targets_length)`
+    (train.py:53,231) returns rnnt + weight * ctc.  The CTC term is the model's auxiliary head (config.model.ctc_weight > 0 builds it) on
+    the audio-encoder states the model's last forward kept (Transducer.ctc_loss_from_last_forward), which are released here: the loop
+    itself stays the reference's, unchanged."""
+
+    def __init__(self, criterion, model, weight):
+        self.criterion, self.model, self.weight = criterion, model, float(weight)
+        if not self.weight > 0.0:
+            raise ValueError("CTCAugmentedCriterion: weight must be > 0, got %r" % (weight,))
+        if getattr(model, "ctc_head", None) is None:
+            raise ValueError("CTCAugmentedCriterion: the model has no CTC head (config.model.ctc_weight > 0 builds it)")
+
+    def __call__(self, logits, targets, inputs_length, targets_length):
+        rnnt = self.criterion(logits, targets, inputs_length, targets_length)
+        ctc = self.model.ctc_loss_from_last_forward(targets, inputs_length, targets_length, reduction=getattr(self.criterion, "reduction", "mean"))
+        return rnnt + self.weight * ctc
+
+    def __getattr__(self, name):
+        return getattr(self.criterion, name)
+
+
 class _Quiet:
     """logger / visualizer stand-in on ranks > 0"""
 
@@ -124,6 +146,9 @@ def main(argv=None):
 
     torch.manual_seed(config.training.seed)                 # the same initial weights everywhere (and rank 0's are broadcast below)
     torch.cuda.manual_seed(config.training.seed)
+    ctc_weight = float(config.training.get('ctc_weight', 0.0) or 0.0)      # joint CTC - transducer training: an optional key of this driver
+    if ctc_weight > 0.0:
+        config.model['ctc_weight'] = ctc_weight             # builds Transducer.ctc_head before the optimiser flattens the parameters
     model = Transducer(config.model).cuda()
     n_params, enc, dec = count_parameters(model)
     logger.info('# the number of parameters in the whole model: %d (encoder %d, decoder %d)' % (n_params, enc, dec))
@@ -139,6 +164,8 @@ def main(argv=None):
         dist.broadcast(se, 0)
         start_epoch = int(se)
     criterion = RNNTLoss(fastemit_lambda=config.training.get('fastemit_lambda', 0.0))     # FastEmit: an optional key of this driver
+    if ctc_weight > 0.0:
+        criterion = CTCAugmentedCriterion(criterion, model, ctc_weight)
     for epoch in range(start_epoch, config.training.epochs):
         if train_sampler is not None:
             train_sampler.set_epoch(epoch)

@@ -130,9 +130,98 @@ def rnnt_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_o
     return grad
 
 
+# ----------------------------------------------------------------------------- CTC loss / greedy decode (auxiliary head on the audio encoder)
+def ctc_workspace(B, T, U, device):
+    f = lib().ttmi_ctc_workspace_bytes
+    f.restype = ctypes.c_size_t
+    n = f(c_int(B), c_int(T), c_int(U))
+    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+
+
+def _ctc_args(logits, labels):
+    if logits.dim() != 3 or logits.dtype is not torch.float32:
+        raise ValueError("ctc: logits must be f32 [B, T, V], got %s %s" % (logits.dtype, tuple(logits.shape)))
+    ld = row_pitch(logits)
+    if ld is None:
+        raise ValueError("ctc: logits must be dense or a [..., :V] view of a row-padded buffer")
+    if labels.dim() != 2 or labels.shape[0] != logits.shape[0] or labels.dtype is not torch.int32 or (labels.numel() and not labels.is_contiguous()):
+        raise ValueError("ctc: labels must be contiguous int32 [B, U]")
+    return ld
+
+
+def ctc_loss_fwd(logits, labels, act_lens, label_lens, blank, workspace):
+    """logits: f32 [B, T, V], dense or row-padded view; labels int32 [B, U] -> costs f32 [B] (include/ttmi.h: ttmi_ctc_loss_fwd)"""
+    _need_cuda(logits, labels, act_lens, label_lens, workspace)
+    ld = _ctc_args(logits, labels)
+    B, T, V = logits.shape
+    costs = torch.empty(B, dtype=torch.float32, device=logits.device)
+    check(lib().ttmi_ctc_loss_fwd(_p(logits), c_long(ld), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(labels.shape[1]),
+                                  c_int(V), c_int(blank), _p(workspace), _p(costs), _stream()), "ttmi_ctc_loss_fwd")
+    return costs
+
+
+def ctc_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, inplace=False):
+    """scale * grad_out[b * grad_out_stride] * d costs[b] / d logits, with the logits' pitch (pad columns zero); inplace: written over the
+    logits"""
+    _need_cuda(logits, labels, act_lens, label_lens, workspace, grad_out)
+    ld = _ctc_args(logits, labels)
+    B, T, V = logits.shape
+    if inplace:
+        grad = logits
+    elif ld == V:
+        grad = torch.empty_like(logits)
+    else:
+        grad = torch.empty(B, T, ld, dtype=logits.dtype, device=logits.device)[..., :V]
+    check(lib().ttmi_ctc_loss_bwd(_p(logits), c_long(ld), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(labels.shape[1]),
+                                  c_int(V), c_int(blank), _p(workspace), _p(grad_out), c_int(grad_out_stride), c_float(scale), _p(grad),
+                                  c_long(ld), _stream()), "ttmi_ctc_loss_bwd")
+    return grad
+
+
+def ctc_greedy(logits, act_lens, blank=0):
+    """logits f32 [B, T, V] (row pitch = stride(-2)), act_lens int32 [B] -> (tokens int32 [B, T], count int32 [B]): per utterance the
+    argmax of its frames with repeats collapsed and blanks dropped in tokens[b, :count[b]]; count[b] = -(1 + t) when frame t has no
+    finite maximum (include/ttmi.h: ttmi_ctc_greedy).  Device only, no synchronisation."""
+    _need_cuda(logits, act_lens)
+    if logits.dim() != 3 or logits.dtype is not torch.float32 or row_pitch(logits) is None:
+        raise ValueError("ctc_greedy: logits must be f32 [B, T, V], dense or row-padded")
+    B, T, V = logits.shape
+    tokens = torch.empty(B, T, dtype=torch.int32, device=logits.device)
+    count = torch.empty(B, dtype=torch.int32, device=logits.device)
+    check(lib().ttmi_ctc_greedy(_p(logits), c_long(row_pitch(logits)), _p(act_lens), c_int(B), c_int(T), c_int(V), c_int(blank), _p(tokens),
+                                _p(count), _stream()), "ttmi_ctc_greedy")
+    return tokens, count
+
+
+def linear_nt(x, w, out, bias=None, prec=0, accumulate=False):
+    """out[M, N] (f32, row pitch = out.stride(0)) (+)= x[M, K] @ w[N, K]^T (+ bias): the library's generic GEMM on f32 operands - exact-f32
+    MFMA in the fp32 mode, the three-term bf16 split in the bf16x3 mode, bf16 MFMA with f32 accumulation and output in the bf16 mode"""
+    M, K = x.shape
+    N = w.shape[0]
+    flags = GEMM_A_KMAJOR | GEMM_B_KMAJOR | (GEMM_BIAS if bias is not None else 0) | _PREC_FLAG[prec]
+    return gemm(x, w, out, M, N, K, x.stride(0), w.stride(0), out.stride(0), flags, bias=bias, beta=1.0 if accumulate else 0.0)
+
+
+def linear_nn(g, w, out, prec=0):
+    """out[M, K] (f32) = g[M, N] @ w[N, K] (a linear layer's input gradient)"""
+    M, N = g.shape
+    K = w.shape[1]
+    return gemm(g, w, out, M, K, N, g.stride(0), w.stride(0), out.stride(0), GEMM_A_KMAJOR | _PREC_FLAG[prec])
+
+
+def linear_tn(g, x, out, prec=0, accumulate=True):
+    """out[N, K] (f32) (+)= g[M, N]^T @ x[M, K] (a linear layer's weight gradient; x [M, 1] of ones: its bias gradient, the column sums
+    of g).  One workgroup walks the whole reduction of a tile: no split along M, no atomics, the same bits in every run."""
+    M, N = g.shape
+    K = x.shape[1]
+    return gemm(g, x, out, N, K, M, g.stride(0), x.stride(0), out.stride(0) if out.dim() == 2 else 1, _PREC_FLAG[prec],
+                beta=1.0 if accumulate else 0.0)
+
+
 # ----------------------------------------------------------------------------- generic GEMM (tests / bring-up)
 GEMM_BIAS, GEMM_RELU, GEMM_ATOMIC, GEMM_MASK_AUX, GEMM_A_KMAJOR, GEMM_B_KMAJOR, GEMM_BF16_MFMA, GEMM_BF16X3 = 1, 2, 4, 8, 16, 32, 64, 128
 _DT = {torch.float32: 0, torch.bfloat16: 1}
+_PREC_FLAG = {0: 0, 1: GEMM_BF16_MFMA, 2: GEMM_BF16X3}       # precision code (tt.transformer.default_precision) -> compute flag of the generic GEMM
 
 
 def gemm(A, B, C, M, N, K, lda, ldb, ldc, flags, bias=None, aux=None, alpha=1.0, beta=0.0, nz1=1, nz2=1,
