@@ -323,6 +323,41 @@ int ttmi_greedy_scan_batch_lp(const void* logits, int dtype, long ld, int B, int
 int ttmi_greedy_advance_lp(unsigned long long* key, int B, int n, int n_hist, long* hist, long ld_hist, int* t, const int* T_len, int* need,
                            int* done, int* count, int* flags, const float* lp, int* frames, float* tok_lp, long ld_det, double* score,
                            void* stream);
+/* Frame-synchronous beam search on the greedy path's probability model (Transducer.beam_decode_batch): each of an utterance's frames takes
+ * one decision, blank or one symbol, against the label state of the tokens so far; the emitting frame is consumed.  ttmi_beam_step takes the
+ * beam of every utterance over ONE frame.  One workgroup per utterance; it allocates nothing, does not synchronise with the host, issues no
+ * memset node and may be captured in a HIP graph.
+ * In: logits [B, W, V] (dtype 0 = f32, 1 = bf16 widened exactly; row pitch ld >= V): row (b, w) = the joint of frame t[b] against the label
+ * state of hypothesis w; blank in [0, V); t, T_len i32 [B]; the beam: score_in f64 [B, W], len_in i32 [B, W] (symbols emitted, the start symbol
+ * not counted), hist_in i64 [B, W, ld_hist] (column 0 = the start symbol, columns 1 .. len = the symbols), and - all four or none -
+ * frames_in i32 / tok_lp_in f32 [B, W, ld_det] (emission frame and log-probability of every symbol) with their _out twins.
+ * Out, in buffers of their own (the caller swaps): score_out, len_out, hist_out (columns 0 .. len_out), frames_out / tok_lp_out (len_out
+ * entries); parent i32 [B, W] = the slot of the old beam the new slot continues; fresh i32 [B, W] = 1 where the slot is its parent extended by
+ * a symbol (it needs a new label state), 0 where it keeps its parent's tokens (and label state).
+ * Limits: 1 <= W <= 32, V >= 2, ld_hist >= the largest len_in + 2 (ld_det >= the largest len_in + 1); the kernel never reads or writes past a
+ * row, whatever len_in says.
+ * Rule, per utterance with t[b] < T_len[b]:
+ *  - lp(w, k) = x[w][k] - lse(row w), in one f32 pass over the row as ttmi_greedy_scan_batch_lp takes it; a row without a finite log-sum-exp
+ *    (a NaN, a +inf, nothing but -inf) has lp = NaN throughout.
+ *  - A slot whose score is -inf (or NaN) is empty: it extends nothing and takes part in no merge.
+ *  - Candidates of every live slot i: its blank extension (tokens_i, score_i + lp(i, blank)) and its symbol extensions
+ *    (tokens_i + k, score_i + lp(i, k)), k != blank; sums in f64.  A candidate score that is NaN counts as -inf.
+ *  - Live slots hold distinct sequences (the caller's contract, kept by this rule), so two candidates spell the same sequence only as the blank
+ *    extension of i and the extension of j by k with tokens_i = tokens_j + k.  Those two are ONE candidate: tokens_i, score = log(exp(a) +
+ *    exp(b)) of the two in f64, counted as a blank extension (parent i, fresh 0); frames / tok_lp are those of whichever of the two had the
+ *    larger score before the merge (the blank side's on a tie): i's own, or j's followed by (t[b], lp(j, k)).  The symbol side enters the merge
+ *    wherever it would rank among j's symbols.
+ *  - The new beam = the W best candidates under the total order: score descending, then parent slot ascending, then blank before symbols,
+ *    then symbol ascending; selected by counting ranks under that order (no atomics on values: two runs give the same bits).  A symbol
+ *    extension has parent i, fresh 1, len_i + 1 tokens and i's details followed by (t[b], lp(i, k)).  Only candidates with a score > -inf
+ *    take a slot; slots left over are empty: score -inf, len 0, parent = the slot itself, fresh 0 (their hist / frames / tok_lp rows are not
+ *    written).
+ * An utterance with t[b] >= T_len[b] is finished: its beam is copied through, parent = identity, fresh = 0.  t is not advanced: the caller does.
+ * A beam starts as slot 0 = (score 0, len 0, hist[0] = start symbol), every other slot empty. */
+int ttmi_beam_step(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len,
+                   const double* score_in, const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in,
+                   double* score_out, int* len_out, long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det,
+                   int* parent, int* fresh, void* stream);
 
 /* ---- feature front-end on the GPU: replaces the data loader's per-utterance numpy code.
  * ttmi_logmel: get_feature / get_feature2 (tt/utils.py:182-207: librosa.feature.melspectrogram(y, sr, n_fft=512, hop_length=160, n_mels), then

@@ -1668,6 +1668,14 @@ int ttmi_greedy_advance_lp(unsigned long long* key, int B, int n, int n_hist, lo
     return greedy_advance_lp(key, B, n, n_hist, hist, ld_hist, t, T_len, need, done, count, flags, lp, frames, tok_lp, ld_det, score,
                              static_cast<hipStream_t>(stream));
 }
+// one frame of the frame-synchronous beam search (Transducer.beam_decode_batch, ttmi.h)
+int ttmi_beam_step(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len,
+                   const double* score_in, const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in,
+                   double* score_out, int* len_out, long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det,
+                   int* parent, int* fresh, void* stream) {
+    return beam_step(logits, dtype, ld, B, W, V, blank, t, T_len, score_in, len_in, hist_in, frames_in, tok_lp_in, score_out, len_out, hist_out,
+                     frames_out, tok_lp_out, ld_hist, ld_det, parent, fresh, static_cast<hipStream_t>(stream));
+}
 
 // ------------------------------------------------------------------ embedding (tt/decoder.py:26,39)
 int ttmi_embed_fwd(const long* tokens, const float* W, long n, int d, int V, float* out, void* stream) {

@@ -1607,7 +1607,240 @@ __global__ void greedy_advance_lp_kernel(unsigned long long* __restrict__ key, i
     if (!done[b]) atomicAdd(flags + 1, 1);
 }
 
+// ---- frame-synchronous beam search (Transducer.beam_decode_batch): one step of the beam of every utterance, on the probability model of the
+// greedy path above (each frame takes one decision, blank or one symbol; the emitting frame is consumed).  The rule is ttmi.h's, at
+// ttmi_beam_step; this is how the kernel walks it.  One workgroup of 4 waves per utterance, everything between the logits and the new beam
+// in LDS:
+//   1. partner[i] = the live slot j with tokens_i = tokens_j + last_i (at most one: live slots hold distinct sequences), found by comparing
+//      the histories from their ends (beams share prefixes, not suffixes);
+//   2. a wave per live row: the row's log-sum-exp in the single f32 pass of greedy_scan_batch_lp_kernel, then the row's W best symbol
+//      candidates under (score desc, symbol asc), one argmax pass per candidate over the entries that come after the previous pick in that
+//      order (the row stays in cache); a pick that is some slot's merge partner's symbol belongs to that slot's blank candidate and is not
+//      listed.  The key is the candidate's own f64 score, so the preselection is exact for the final order;
+//   3. a thread per slot: its blank candidate, with the partner's symbol extension folded in (log-sum in f64);
+//   4. rank counting over the W (W + 1) candidates: table index order IS (parent asc, blank first, symbols as picked), so a candidate's
+//      rank is the number of candidates with a larger score, or an equal one and a lower index.  No atomics on values: same bits every run;
+//   5. a wave per new slot copies tokens and details from its parent(s).
+constexpr int BEAM_MAX_W = 32;
+struct BeamStepArgs {
+    const void* logits; long ld; int W, V, blank;
+    const int *t, *T_len;
+    const double* score_in; const int* len_in; const long* hist_in; const int* frames_in; const float* tok_lp_in;
+    double* score_out; int* len_out; long* hist_out; int* frames_out; float* tok_lp_out;
+    long ld_hist, ld_det;
+    int *parent, *fresh;
+};
+__device__ __forceinline__ double beam_key(double s) { return s > -INFINITY ? s : -INFINITY; }      // NaN ranks as -inf
+template <typename TL>
+__device__ __forceinline__ float beam_load(const TL* p) {
+    if constexpr (sizeof(TL) == 4) return *p;
+    else return bf16_to_f32(*p);
+}
+// new slot `dst` = tokens of slot `src` (columns 0 .. n_tok), details of slot `dsrc` (n_det entries), then optionally one token / one detail
+__device__ __forceinline__ void beam_copy_slot(const BeamStepArgs& a, long base, int dst, int src, int n_tok, long app_tok, int dsrc, int n_det,
+                                               bool app_det, int app_frame, float app_lp, int lane) {
+    const long* hi = a.hist_in + (base + src) * a.ld_hist;
+    long* ho = a.hist_out + (base + dst) * a.ld_hist;
+    for (int c = lane; c <= n_tok && c < a.ld_hist; c += 64) ho[c] = hi[c];
+    if (app_tok >= 0 && lane == 0 && n_tok + 1 < a.ld_hist) ho[n_tok + 1] = app_tok;
+    if (!a.frames_out) return;
+    const int* fi = a.frames_in + (base + dsrc) * a.ld_det;
+    const float* li = a.tok_lp_in + (base + dsrc) * a.ld_det;
+    int* fo = a.frames_out + (base + dst) * a.ld_det;
+    float* lo = a.tok_lp_out + (base + dst) * a.ld_det;
+    for (int c = lane; c < n_det && c < a.ld_det; c += 64) { fo[c] = fi[c]; lo[c] = li[c]; }
+    if (app_det && lane == 0 && n_det < a.ld_det) { fo[n_det] = app_frame; lo[n_det] = app_lp; }
+}
+template <typename TL>
+__global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
+    constexpr int MW = BEAM_MAX_W, NC = MW * (MW + 1);
+    __shared__ double s_score[MW], c_score[NC];
+    __shared__ float s_lse[MW], c_lp[NC], s_mlp[MW];
+    __shared__ int s_len[MW], s_partner[MW], s_msym[MW], c_sym[NC], s_win[MW];
+    __shared__ long s_last[MW];
+    const int b = blockIdx.x, W = a.W, V = a.V, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nc = W * (W + 1);
+    const long base = (long)b * W;
+    const int tb = a.t[b];
+    if (tb >= a.T_len[b]) {                                  // (block-uniform) finished: the beam passes through
+        for (int w = wave; w < W; w += 4) {
+            const int n = max(a.len_in[base + w], 0);
+            beam_copy_slot(a, base, w, w, n, -1, w, n, false, 0, 0.f, lane);
+            if (lane == 0) {
+                a.score_out[base + w] = a.score_in[base + w];
+                a.len_out[base + w] = a.len_in[base + w];
+                a.parent[base + w] = w;
+                a.fresh[base + w] = 0;
+            }
+        }
+        return;
+    }
+    if (tid < W) {
+        const double s = a.score_in[base + tid];
+        const int n = a.len_in[base + tid];
+        const bool live = s > -INFINITY && n >= 0 && n < a.ld_hist;
+        s_score[tid] = live ? s : -INFINITY;                 // an empty slot extends nothing and takes part in no merge
+        s_len[tid] = live ? n : 0;
+        s_last[tid] = (live && n >= 1) ? a.hist_in[(base + tid) * a.ld_hist + n] : -1;
+        s_partner[tid] = MW;
+        s_msym[tid] = -1;
+        s_lse[tid] = NAN;
+        s_win[tid] = -1;
+    }
+    for (int c = tid; c < nc; c += 256) { c_score[c] = -INFINITY; c_sym[c] = -1; c_lp[c] = 0.f; }
+    __syncthreads();
+    // 1. merge partners
+    for (int p = tid; p < W * W; p += 256) {
+        const int i = p / W, j = p - i * W;
+        if (!(s_score[i] > -INFINITY) || !(s_score[j] > -INFINITY) || s_len[i] != s_len[j] + 1) continue;
+        const long* hi = a.hist_in + (base + i) * a.ld_hist;
+        const long* hj = a.hist_in + (base + j) * a.ld_hist;
+        bool same = true;
+        for (int c = s_len[j]; c >= 1 && same; --c) same = hi[c] == hj[c];
+        if (same) atomicMin(&s_partner[i], j);               // (integer: the same result in every run, also on a beam that breaks the contract)
+    }
+    __syncthreads();
+    if (tid < W && s_partner[tid] < MW && s_last[tid] >= 0 && s_last[tid] < V && s_last[tid] != a.blank) s_msym[tid] = (int)s_last[tid];
+    __syncthreads();
+    // 2. log-sum-exp and symbol candidates of every live row
+    for (int w = wave; w < W; w += 4) {
+        const double sw = s_score[w];
+        if (!(sw > -INFINITY)) continue;                     // (wave-uniform)
+        const TL* p = static_cast<const TL*>(a.logits) + (base + w) * a.ld;
+        float m = -INFINITY, s = 0.f;
+        for (int v = lane; v < V; v += 64) {
+            const float x = beam_load(p + v);
+            if (x != -INFINITY) {
+                const float e = __expf(-fabsf(x - m));
+                if (x > m) { s = s * e + 1.f; m = x; }
+                else s += e;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+            const float nm = fmaxf(m, om);
+            s = s * (m == nm ? 1.f : __expf(m - nm)) + os * (om == nm ? 1.f : __expf(om - nm));
+            m = nm;
+        }
+        const float lse = __shfl(m + logf(s), 0, 64);        // ONE value for the row: the lanes' copies of (m, s) may differ in the last ulp
+        if (!(lse - lse == 0.f)) continue;                   // a NaN, a +inf or nothing but -inf in the row: every candidate of it scores NaN
+        if (lane == 0) s_lse[w] = lse;
+        double ps = INFINITY;                                // the previous pick: candidates after it in (score desc, symbol asc) remain
+        int pk = -1, cnt = 0;
+        while (cnt < W) {
+            double bs = -INFINITY;
+            int bk = 0x7fffffff;
+            float bl = 0.f;
+            for (int v = lane; v < V; v += 64) {
+                if (v == a.blank) continue;
+                const float l = beam_load(p + v) - lse;
+                const double sc = beam_key(sw + (double)l);
+                if ((sc < ps || (sc == ps && v > pk)) && (sc > bs || (sc == bs && v < bk))) { bs = sc; bk = v; bl = l; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double os = __shfl_xor(bs, o, 64);
+                const int ok = __shfl_xor(bk, o, 64);
+                const float ol = __shfl_xor(bl, o, 64);
+                if (os > bs || (os == bs && ok < bk)) { bs = os; bk = ok; bl = ol; }
+            }
+            if (!(bs > -INFINITY)) break;                    // nothing with a probability left (bk = 0x7fffffff: nothing left at all)
+            ps = bs; pk = bk;
+            bool merged = false;
+            for (int i = 0; i < W; ++i) merged |= s_partner[i] == w && s_msym[i] == bk;
+            if (merged) continue;
+            if (lane == 0) {
+                const int c = w * (W + 1) + 1 + cnt;
+                c_score[c] = bs; c_sym[c] = bk; c_lp[c] = bl;
+            }
+            ++cnt;
+        }
+    }
+    __syncthreads();
+    // 3. blank candidates, the partner's symbol extension folded in
+    if (tid < W && s_score[tid] > -INFINITY && s_lse[tid] == s_lse[tid]) {
+        const int i = tid, j = s_partner[i];
+        const TL* pi = static_cast<const TL*>(a.logits) + (base + i) * a.ld;
+        double sc = beam_key(s_score[i] + (double)(beam_load(pi + a.blank) - s_lse[i]));
+        int from_symbol = 0;
+        if (s_msym[i] >= 0 && s_lse[j] == s_lse[j]) {
+            const TL* pj = static_cast<const TL*>(a.logits) + (base + j) * a.ld;
+            const float l = beam_load(pj + s_msym[i]) - s_lse[j];
+            const double ss = beam_key(s_score[j] + (double)l);
+            if (ss > -INFINITY) {
+                from_symbol = ss > sc;                       // the details are those of the larger of the two, the blank side's on a tie
+                const double hi = from_symbol ? ss : sc, lo = from_symbol ? sc : ss;
+                sc = hi + log1p(exp(lo - hi));               // (lo = -inf adds 0)
+                s_mlp[i] = l;
+            }
+        }
+        c_score[i * (W + 1)] = sc;
+        c_sym[i * (W + 1)] = -1 - from_symbol;               // -1: blank; -2: blank with the details of the merged symbol extension
+    } else if (tid < W && s_score[tid] > -INFINITY) {
+        // this row has no finite log-sum-exp, but a partner's symbol extension still spells this slot's tokens
+        const int i = tid, j = s_partner[i];
+        if (s_msym[i] >= 0 && s_lse[j] == s_lse[j]) {
+            const TL* pj = static_cast<const TL*>(a.logits) + (base + j) * a.ld;
+            const float l = beam_load(pj + s_msym[i]) - s_lse[j];
+            c_score[i * (W + 1)] = beam_key(s_score[j] + (double)l);
+            c_sym[i * (W + 1)] = -2;
+            s_mlp[i] = l;
+        }
+    }
+    __syncthreads();
+    // 4. rank counting
+    for (int c = tid; c < nc; c += 256) {
+        const double sc = c_score[c];
+        if (!(sc > -INFINITY)) continue;
+        int rank = 0;
+        for (int o = 0; o < nc; ++o) {
+            const double so = c_score[o];
+            rank += (so > sc) | ((so == sc) & (o < c));
+        }
+        if (rank < W) s_win[rank] = c;
+    }
+    __syncthreads();
+    // 5. the new beam
+    for (int r = wave; r < W; r += 4) {
+        const int c = s_win[r];
+        if (c < 0) {                                         // fewer candidates with a probability than slots: an empty slot
+            if (lane == 0) { a.score_out[base + r] = -INFINITY; a.len_out[base + r] = 0; a.parent[base + r] = r; a.fresh[base + r] = 0; }
+            continue;
+        }
+        const int i = c / (W + 1), sym = c_sym[c], n = s_len[i];
+        if (sym >= 0) beam_copy_slot(a, base, r, i, n, sym, i, n, true, tb, c_lp[c], lane);
+        else if (sym == -1) beam_copy_slot(a, base, r, i, n, -1, i, n, false, 0, 0.f, lane);
+        else beam_copy_slot(a, base, r, i, n, -1, s_partner[i], n - 1, true, tb, s_mlp[i], lane);
+        if (lane == 0) {
+            a.score_out[base + r] = c_score[c];
+            a.len_out[base + r] = sym >= 0 ? n + 1 : n;
+            a.parent[base + r] = i;
+            a.fresh[base + r] = sym >= 0;
+        }
+    }
+}
+
 }  // namespace
+
+int beam_step(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len, const double* score_in,
+              const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in, double* score_out, int* len_out,
+              long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det, int* parent, int* fresh, hipStream_t st) {
+    TTMI_REQUIRE(logits && t && T_len && score_in && len_in && hist_in && score_out && len_out && hist_out && parent && fresh,
+                 "beam_step: null pointer");
+    const int n_det = !!frames_in + !!tok_lp_in + !!frames_out + !!tok_lp_out;
+    TTMI_REQUIRE(n_det == 0 || n_det == 4, "beam_step: frames / tok_lp come as all four arrays or none");
+    TTMI_REQUIRE(dtype == 0 || dtype == 1, "beam_step: logits are f32 (0) or bf16 (1)");
+    TTMI_REQUIRE(W >= 1 && W <= BEAM_MAX_W, "beam_step: beam width %d outside [1, %d]", W, BEAM_MAX_W);
+    TTMI_REQUIRE(B > 0 && V >= 2 && ld >= V && blank >= 0 && blank < V && ld_hist >= 2 && (n_det == 0 || ld_det >= 1), "beam_step: bad arguments");
+    TTMI_REQUIRE(score_in != score_out && len_in != len_out && hist_in != hist_out && (n_det == 0 || (frames_in != frames_out && tok_lp_in != tok_lp_out)),
+                 "beam_step: the new beam needs buffers of its own");
+    BeamStepArgs a{logits, ld, W, V, blank, t, T_len, score_in, len_in, hist_in, frames_in, tok_lp_in, score_out, len_out, hist_out, frames_out,
+                   tok_lp_out, ld_hist, ld_det, parent, fresh};
+    if (dtype == 0) hipLaunchKernelGGL(beam_step_kernel<float>, dim3(B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(beam_step_kernel<bf16_t>, dim3(B), dim3(256), 0, st, a);
+    TTMI_LAUNCH_CHECK("beam_step_kernel");
+    return TTMI_OK;
+}
 
 int greedy_scan_batch(const void* logits, int dtype, long ld, int B, int n, int V, int blank, const int* t, const int* T_len, const int* need,
                       unsigned long long* key, hipStream_t st) {

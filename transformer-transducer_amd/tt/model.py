@@ -3,6 +3,7 @@ forward(inputs[B,T,d], targets[B,U]) -> logits[B,T,U+1,V], decode/recognize (gre
 import collections
 import copy
 import heapq
+import math
 import os
 
 import numpy as np
@@ -490,7 +491,10 @@ details=False returns), `frames` (list of int, the frame at which each token was
 log P(token) on its emission frame) and `score` (float): the log-probability of the decisions the greedy decoder took, one term per frame of the
 utterance - blank's log-probability against the label state current at that frame on a frame that does not emit, the token's on a frame that does.
 That is the path of this decoder (at most one symbol per frame, the emitting frame is consumed), NOT a path of the RNN-T lattice, which follows a
-label with a blank on the same frame: `score` is not comparable with `Transducer.align(...).score`."""
+label with a blank on the same frame: `score` is not comparable with `Transducer.align(...).score`.
+Beam decoding (beam_decode_batch / recognize_nbest) returns lists of the same type on the same probability model: there `score` is the log of the summed
+probability of every decision sequence the beam kept for `tokens` (hypotheses spelling the same tokens are merged), `frames` and `logprobs` those of the
+best single one of them."""
 
 
 class JointNet(nn.Module):
@@ -1020,6 +1024,94 @@ class Transducer(nn.Module):
         if enc_states.is_cuda and inputs.size(0) > 1 and self.config.batched_decode is not False:
             return self.decode_batch(enc_states, inputs_length)
         return [self.decode(enc_states[b], inputs_length[b]) for b in range(inputs.size(0))]
+
+    @torch.no_grad()
+    def beam_decode_batch(self, enc_states, lengths, beam_width=4, nbest=None):
+        """Frame-synchronous beam search of EVERY utterance of a batch at once -> per utterance a list of at most `nbest` (default: beam_width)
+        DecodeResult, best first.  The probability model is the greedy decoder's (`decode_batch`): each of an utterance's T_b frames takes one
+        decision, blank or one symbol, against the label state of the tokens so far, and the emitting frame is consumed.  Unlike `beam_search`
+        (the reference's, kept for token identity) every frame adds its term to every hypothesis, hypotheses that spell the same tokens are
+        merged (their probabilities add), and the scores of the list are comparable: `score` = the log of the summed probability of the
+        decision sequences the beam kept for these tokens, `frames` / `logprobs` = those of the best single one (include/ttmi.h,
+        ttmi_beam_step, has the rule).  The loop runs over frames 0 .. max(lengths) - 1; per frame ONE joint call scores frame t of every
+        utterance against the [B, beam_width, d] table of label states, ttmi_beam_step turns the logits into the next beam on the device
+        (one workgroup per utterance), ONE host read brings the new slots' lengths and which of them are new sequences, and the label encoder
+        runs on those only, one call per distinct history length (the relative-position term depends on the sequence length, see
+        `decode_batch`); every other slot takes its parent's state by a gather on the device.  Finished utterances pass through unchanged.
+        Not built: a cache of label states for sequences seen on earlier frames, a captured graph of the loop, a streaming variant."""
+        if not enc_states.is_cuda:
+            raise ValueError("beam_decode_batch: enc_states must live on the GPU (the MI355X build has no CPU path)")
+        W = int(beam_width)
+        nbest = W if nbest is None else int(nbest)
+        if not 1 <= W <= 32 or nbest < 1:
+            raise ValueError("beam_decode_batch: beam_width must be in [1, 32] and nbest >= 1, got %r and %r" % (beam_width, nbest))
+        dev = enc_states.device
+        B, T = enc_states.shape[0], enc_states.shape[1]
+        lens = [T] * B if lengths is None else [min(int(v), T) for v in torch.as_tensor(lengths).tolist()]
+        T_max = max(lens + [0])
+        T_len = torch.tensor(lens, dtype=torch.int32, device=dev)
+        t = torch.zeros(B, dtype=torch.int32, device=dev)
+        ld_hist, ld_det = T_max + 2, T_max + 1                       # at most one symbol per frame; column 0 = the start symbol (blank)
+
+        def beam():
+            """score, (len | fresh) packed for the one host read, histories, emission frames, token log-probabilities"""
+            return dict(score=torch.full((B, W), -math.inf, dtype=torch.float64, device=dev), meta=torch.zeros(2, B, W, dtype=torch.int32, device=dev),
+                        hist=torch.zeros(B, W, ld_hist, dtype=torch.long, device=dev), frames=torch.zeros(B, W, ld_det, dtype=torch.int32, device=dev),
+                        tok_lp=torch.zeros(B, W, ld_det, dtype=torch.float32, device=dev))
+
+        def arrays(bm):
+            return bm["score"], bm["meta"][0], bm["hist"], bm["frames"], bm["tok_lp"]
+        cur, nxt = beam(), beam()
+        cur["score"][:, 0] = 0.0                                     # slot 0 holds the start symbol, the other slots are empty
+        parent = torch.zeros(B, W, dtype=torch.int32, device=dev)
+        start = self.decoder(torch.zeros(1, 1, dtype=torch.long, device=dev))[:, -1, :]
+        states = start[None].expand(B, W, -1).contiguous()           # [B, W, d]; what an empty slot holds is never read by the kernel
+        d = states.shape[-1]
+        for f in range(T_max):
+            logits = self.joint(enc_states[:, f:f + 1].contiguous(), states)                      # [B, 1, W, V]
+            ops.beam_step(logits[:, 0], t, T_len, arrays(cur), arrays(nxt), parent, nxt["meta"][1], blank=0)
+            t += 1
+            cur, nxt = nxt, cur
+            if f == T_max - 1:
+                break
+            n_tok, fresh = cur["meta"].cpu().tolist()                                             # the frame's one host round trip
+            states = states.gather(1, parent.long()[:, :, None].expand(-1, -1, d))                # a slot that keeps its tokens keeps its label state
+            by_len = {}
+            for b in range(B):
+                if f + 1 >= lens[b] or not any(fresh[b]):                                         # (an utterance without frames left reads no label state again)
+                    continue
+                for w in range(W):
+                    if fresh[b][w]:
+                        by_len.setdefault(n_tok[b][w], []).append(b * W + w)
+            for n, rows in sorted(by_len.items()):
+                rows = torch.tensor(rows, dtype=torch.long, device=dev)
+                hist = cur["hist"].view(B * W, ld_hist)[rows, :n + 1]
+                states.view(B * W, d).index_copy_(0, rows, self.decoder(hist.contiguous())[:, -1, :])
+        # ONE transfer, as f64 (exact for token ids, counts, frames and f32 log-probabilities): score | len | tokens | frames | logprobs
+        packed = torch.cat([cur["score"][:, :, None], cur["meta"][0].double()[:, :, None], cur["hist"][:, :, 1:].double(), cur["frames"].double(),
+                            cur["tok_lp"].double()], dim=2).cpu()
+        out = []
+        for b in range(B):
+            res = []
+            for w in range(W):
+                score, c = float(packed[b, w, 0]), int(packed[b, w, 1])
+                if not score > -math.inf:                            # an empty slot
+                    continue
+                tok, frm, lpr = (packed[b, w, 2 + i * ld_det:2 + i * ld_det + c].tolist() for i in range(3))
+                res.append(DecodeResult([int(v) for v in tok], [int(v) for v in frm], lpr, score))
+            if not res or not math.isfinite(res[0].score):
+                raise RuntimeError("beam search: utterance %d has no hypothesis with a finite score (NaN logits?)" % b)
+            out.append(res[:nbest])
+        return out
+
+    @torch.no_grad()
+    def recognize_nbest(self, inputs, inputs_length=None, audio_mask=None, beam_width=4, nbest=None):
+        """N-best recognition of a batch: the encoder, then `beam_decode_batch` -> per utterance a list of at most `nbest` (default:
+        beam_width) DecodeResult, best first, with merged, comparable scores"""
+        if not inputs.is_cuda:
+            raise ValueError("recognize_nbest: inputs must live on the GPU (the MI355X build has no CPU path)")
+        enc_states = self.encoder(inputs, audio_mask)
+        return self.beam_decode_batch(enc_states, inputs_length, beam_width=beam_width, nbest=nbest)
 
     @torch.no_grad()
     def beam_search(self, enc_state, lengths, beam_width=5, block=64):

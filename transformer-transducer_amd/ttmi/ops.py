@@ -938,3 +938,30 @@ def greedy_advance_lp(key, n, n_hist, hist, t, T_len, need, done, count, flags, 
     check(lib().ttmi_greedy_advance_lp(_p(key), c_int(B), c_int(n), c_int(n_hist), _p(hist), c_long(hist.stride(0)), _p(t), _p(T_len), _p(need),
                                        _p(done), _p(count), _p(flags), _p(lp), _p(frames), _p(tok_lp), c_long(frames.stride(0)), _p(score),
                                        _stream()), "ttmi_greedy_advance_lp")
+
+
+def beam_step(logits, t, T_len, beam_in, beam_out, parent, fresh, blank=0):
+    """one frame of the frame-synchronous beam search of every utterance (include/ttmi.h: ttmi_beam_step, the rule is written there).
+    logits [B, W, V] (f32 / bf16, row pitch = stride(-2)) = the joint of frame t[b] against the label state of every hypothesis; beam_in /
+    beam_out = (score f64 [B, W], len i32 [B, W], hist i64 [B, W, ld_hist], frames i32 [B, W, ld_det] or None, tok_lp f32 [B, W, ld_det] or
+    None), two sets of buffers the caller swaps; parent / fresh i32 [B, W].  Device only, no synchronisation."""
+    B, W, V = logits.shape
+    (s0, n0, h0, f0, l0), (s1, n1, h1, f1, l1) = beam_in, beam_out
+    _need_cuda(logits, t, T_len, s0, n0, h0, f0, l0, s1, n1, h1, f1, l1, parent, fresh)
+    if logits.stride(-1) != 1 or (B > 1 and logits.stride(0) != W * logits.stride(1)):
+        raise ValueError("beam_step: logits rows must be evenly pitched ([B, W, V] with stride(0) = W * stride(1))")
+    for x in (t, T_len):
+        assert x.dtype is torch.int32 and x.is_contiguous() and x.shape[0] == B
+    for s, n, h, f, l in (beam_in, beam_out):
+        assert s.dtype is torch.float64 and s.is_contiguous() and tuple(s.shape) == (B, W)
+        assert n.dtype is torch.int32 and n.is_contiguous() and tuple(n.shape) == (B, W)
+        assert h.dtype is torch.long and h.is_contiguous() and tuple(h.shape[:2]) == (B, W) and h.shape == h0.shape
+        assert (f is None) == (l is None) == (f0 is None)
+        if f is not None:
+            assert f.dtype is torch.int32 and l.dtype is torch.float32 and f.is_contiguous() and l.is_contiguous()
+            assert tuple(f.shape[:2]) == (B, W) and f.shape == l.shape == f0.shape
+    for x in (parent, fresh):
+        assert x.dtype is torch.int32 and x.is_contiguous() and tuple(x.shape) == (B, W)
+    check(lib().ttmi_beam_step(_p(logits), c_int(_DT[logits.dtype]), c_long(logits.stride(-2)), c_int(B), c_int(W), c_int(V), c_int(blank), _p(t),
+                               _p(T_len), _p(s0), _p(n0), _p(h0), _p(f0), _p(l0), _p(s1), _p(n1), _p(h1), _p(f1), _p(l1), c_long(h0.shape[2]),
+                               c_long(f0.shape[2] if f0 is not None else 0), _p(parent), _p(fresh), _stream()), "ttmi_beam_step")
