@@ -359,6 +359,25 @@ int ttmi_beam_step(const void* logits, int dtype, long ld, int B, int W, int V, 
                    double* score_out, int* len_out, long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det,
                    int* parent, int* fresh, void* stream);
 
+/* ---- error counting (ttmi.metrics: evaluation, and the per-hypothesis error counts of minimum word error rate training).
+ * ttmi_edit_distance: token edit distance of P (hypothesis, transcript) pairs with its substitution / deletion / insertion counts.  One wave
+ * per pair; it allocates nothing, does not synchronise with the host, uses no floating point and no atomics (two runs give the same bits).
+ * In: hyp i32 [P, ld_hyp], hyp_len i32 [P]; ref i32 [n_ref, ld_ref], ref_len i32 [n_ref]; ref_index i32 [P] or NULL.  Pair p compares
+ * hyp[p, :hyp_len[p]] with ref[r, :ref_len[r]], r = ref_index ? ref_index[p] : p (the N hypotheses of an utterance share one transcript
+ * row).  Tokens are compared by equality only: any int32 value is a token.
+ * Out: out i32 [P, 4] = (distance, substitutions, deletions, insertions); a deletion is a ref token without a hyp counterpart, an insertion a
+ * hyp token without a ref counterpart, so distance = s + d + i and hyp_len = ref_len - d + i.
+ * Limits: 0 <= max_hyp, max_ref <= 1024 (the lattice's own limit) and max_hyp <= ld_hyp, max_ref <= ld_ref; P >= 0, n_ref >= 0; no null
+ * pointer (ref_index excepted) - else rc < 0 with a ttmi_last_error text, before any launch.  P = 0 succeeds and does nothing.
+ * A pair whose hyp_len is outside [0, max_hyp], whose ref_index (or p, without one) is outside [0, n_ref) or whose ref_len is outside
+ * [0, max_ref] is out of contract: it reads no token and writes (-1, -1, -1, -1); its neighbours are unaffected.
+ * Rule: among all alignments the one that minimises (distance, substitutions, deletions, insertions) LEXICOGRAPHICALLY - the counts are
+ * unique.  Equivalently the shortest path through the alignment grid with the integer edge costs
+ *     match 0,  substitution (1 << 48) + (1 << 32),  deletion (1 << 48) + (1 << 16),  insertion (1 << 48) + 1
+ * in int64; the four fields are read back from the path cost (bits 48.., 32..47, 16..31, 0..15: every field of a path is <= 2048). */
+int ttmi_edit_distance(const int* hyp, long ld_hyp, const int* hyp_len, const int* ref, long ld_ref, const int* ref_len,
+                       const int* ref_index /* nullable */, int P, int n_ref, int max_hyp, int max_ref, int* out /* [P, 4] */, void* stream);
+
 /* ---- feature front-end on the GPU: replaces the data loader's per-utterance numpy code.
  * ttmi_logmel: get_feature / get_feature2 (tt/utils.py:182-207: librosa.feature.melspectrogram(y, sr, n_fft=512, hop_length=160, n_mels), then
  * log) for a batch.  wave i16 [B, pitch >= nmax] zero padded, n_samples i32 [B] (device) -> out f32 [B, Fmax, n_mels], Fmax = 1 + nmax / hop,

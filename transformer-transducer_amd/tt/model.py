@@ -122,9 +122,13 @@ class _JointLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, enc, dec, wf, bf, wp, bp, labels, act_lens, label_lens, prec, chunk, reduction, exp_state, grad_mode=True, blank=0,
-                fastemit_lambda=0.0):
+                fastemit_lambda=0.0, weights=None):
         """exp_state: None (plain fused form) or the JointNet's _ExpShift for this device (exp-domain form); fastemit_lambda: the FastEmit
-        weight of the loss gradient (warprnnt_pytorch.RNNTLoss), in all three chunk forms"""
+        weight of the loss gradient (warprnnt_pytorch.RNNTLoss), in all three chunk forms; weights: None or a constant f32 [B] on the device,
+        one factor per utterance: the result is sum_b w_b cost_b (times 1 / B for 'mean') and every chunk's loss-gradient call reads its slice
+        of w as its upstream gradient (grad_out_stride = 1), so the gradients formed here are those of the weighted sum.  A chunk whose
+        weights are all zero is NOT skipped: its costs are part of the result either way, and knowing that its weights are zero would take a
+        host read of a device tensor - its gradient kernels run and add exact zeros"""
         fe = ops.check_fastemit(fastemit_lambda)
         enc, dec = enc.contiguous(), dec.contiguous()
         params = (wf, bf, wp, bp)
@@ -139,6 +143,10 @@ class _JointLossFn(torch.autograd.Function):
             denc, ddec = torch.empty_like(enc), torch.empty_like(dec)
             g = {n: torch.zeros_like(t) for n, t in zip(("wf", "bf", "wp", "bp"), params)}
         J, V = wf.shape[0], wp.shape[0]
+
+        def upstream(c0, c1):
+            """(grad_out, grad_out_stride) of a chunk's loss-gradient call: the shared 1, or the chunk's utterance weights"""
+            return (one, 0) if weights is None else (weights[c0:c1], 1)
         st = exp_state
         exp_ran = seeded = False
         capturing = enc.is_cuda and torch.cuda.is_current_stream_capturing()      # (ttmi.train.GraphedStep looks at the flag between replays)
@@ -157,7 +165,7 @@ class _JointLossFn(torch.autograd.Function):
                 P, rowsum, saved, emis = ops.joint_fwd_exp(enc[c0:c1], dec[c0:c1], wf_, bf_, wp_, bp_, prec, st.cur, lab.contiguous(), blank)
                 costs[c0:c1] = ops.rnnt_loss_fwd_exp(P, rowsum, lab, al, ll, blank, ws, st.cur, st.nxt, emis, st.flag)
                 if need:
-                    srow, srow16 = ops.rnnt_loss_bwd_exp(P, lab, al, ll, blank, ws, one, 0, scale, fastemit_lambda=fe)
+                    srow, srow16 = ops.rnnt_loss_bwd_exp(P, lab, al, ll, blank, ws, *upstream(c0, c1), scale, fastemit_lambda=fe)
                     ops.joint_bwd_exp(P, srow, srow16, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
                 del P, rowsum, saved, emis
                 exp_ran = True
@@ -169,10 +177,10 @@ class _JointLossFn(torch.autograd.Function):
                 seeded = True
             if need and ops.joint_loss_split_supported(logits, wf_.shape[0], prec):
                 # bf16x3: the gradient leaves the loss kernel as the two bf16 planes the joint's three-term backward multiplies (round 6: no split pass over d logits)
-                planes = ops.rnnt_loss_bwd_split(logits, lab, al, ll, blank, ws, one, 0, scale, fastemit_lambda=fe)
+                planes = ops.rnnt_loss_bwd_split(logits, lab, al, ll, blank, ws, *upstream(c0, c1), scale, fastemit_lambda=fe)
                 ops.joint_bwd_split(planes, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
             elif need:
-                grad = ops.rnnt_loss_bwd(logits, lab, al, ll, blank, ws, one, 0, scale, inplace=True, fastemit_lambda=fe)
+                grad = ops.rnnt_loss_bwd(logits, lab, al, ll, blank, ws, *upstream(c0, c1), scale, inplace=True, fastemit_lambda=fe)
                 ops.joint_bwd(grad, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
             del logits, saved
         if st is not None and (exp_ran or seeded):
@@ -186,6 +194,8 @@ class _JointLossFn(torch.autograd.Function):
         ctx.params = params
         if reduction == "none":
             return costs
+        if weights is not None:
+            return (costs * weights).sum().reshape(1) * scale
         return costs.sum().reshape(1) * scale
 
     @staticmethod
@@ -205,7 +215,7 @@ class _JointLossFn(torch.autograd.Function):
                     cb()
             else:
                 rets.append(gp * gout)
-        return (denc * gout, ddec * gout, *rets, None, None, None, None, None, None, None, None, None, None)
+        return (denc * gout, ddec * gout, *rets, None, None, None, None, None, None, None, None, None, None, None)
 
 
 class _CTCHeadLossFn(torch.autograd.Function):
@@ -497,6 +507,13 @@ probability of every decision sequence the beam kept for `tokens` (hypotheses sp
 best single one of them."""
 
 
+MWERDetails = collections.namedtuple("MWERDetails", ["hypotheses", "errors", "posteriors", "costs", "expected_errors"])
+MWERDetails.__doc__ = """What Transducer.mwer_loss(details=True) returns beside the loss: `hypotheses` (the token lists used, per utterance), and over the rows
+of the call (hypothesis rows utterance by utterance, then one transcript row per utterance when rnnt_weight > 0) `errors` (i32, edit distance to
+the transcript), `posteriors` (f64, softmax of -cost within the utterance; 0 on a transcript row) and `costs` (f32, RNN-T lattice cost);
+`expected_errors` (f64 [B]) = sum_i P_i W_i per utterance."""
+
+
 class JointNet(nn.Module):
     """logits = project_layer(tanh(forward_layer(cat(enc, dec)))) evaluated in split-weight form
     (forward_layer.weight = [W_enc | W_dec]); accepts [B,T,de]/[B,U,dd] (lattice) or two 1-D vectors (decode)."""
@@ -640,7 +657,7 @@ class Transducer(nn.Module):
         return self.joint(enc_state, dec_state)
 
     def loss(self, inputs, inputs_length, targets, targets_length, reduction="mean", chunk=None, check_lengths=True, exp_domain=False, *,
-             fastemit_lambda=0.0, ctc_weight=None):
+             fastemit_lambda=0.0, ctc_weight=None, utterance_weights=None):
         """Opt-in fused form of train.py:51-53 (`logits = model(inputs, targets); loss = criterion(logits, targets.int(),
         inputs_length.int(), targets_length.int())`) that never materialises the logits (API precedent: tt_espnet/model.py:35-81 returns
         the loss from forward).  Same numbers as the two-call form: the same kernels run, one chunk of `chunk` utterances at a time
@@ -656,10 +673,17 @@ class Transducer(nn.Module):
         fastemit_lambda: FastEmit regularisation of the gradient, as in warprnnt_pytorch.RNNTLoss (the loss value is unchanged).
 
         ctc_weight (None: config.ctc_weight): > 0 returns rnnt + ctc_weight * ctc, the CTC loss of the auxiliary head (`ctc_head`, built when
-        config.ctc_weight > 0) on the same audio-encoder states - the encoder runs once.  ValueError on a module without the head."""
+        config.ctc_weight > 0) on the same audio-encoder states - the encoder runs once.  ValueError on a module without the head.
+
+        utterance_weights (None: today's code path and bits): an f32 / f64 tensor [B] on the device, one constant factor per utterance (no
+        gradient flows into it; zero and negative entries are allowed).  The transducer term becomes sum_b w_b cost_b for 'sum' and that
+        over B for 'mean'; its gradient is formed in the forward pass as always, each chunk's loss-gradient kernel reading its slice of w
+        (all three chunk forms).  ValueError with reduction='none'.  The CTC term, when asked for, is not weighted."""
         from warprnnt_pytorch import check_lengths as certify
         fastemit_lambda = ops.check_fastemit(fastemit_lambda)
         ctc_weight = self._ctc_weight(ctc_weight)
+        if utterance_weights is not None:
+            utterance_weights = self._utterance_weights(utterance_weights, inputs.shape[0], reduction)
         enc_state, dec_state = self._encode(inputs, targets)
         B, T, U1 = enc_state.shape[0], enc_state.shape[1], dec_state.shape[1]
         labels, al, ll = (t.to(device=enc_state.device, dtype=torch.int32).contiguous() for t in (targets, inputs_length, targets_length))
@@ -672,10 +696,21 @@ class Transducer(nn.Module):
         rnnt = _JointLossFn.apply(enc_state, dec_state, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
                                   j.project_layer.bias, labels, al, ll, prec, int(chunk), reduction,
                                   j.exp_shift_state(enc_state.device) if exp_domain and prec == 1 else None, torch.is_grad_enabled(), 0,
-                                  fastemit_lambda)
+                                  fastemit_lambda, utterance_weights)
         if ctc_weight > 0.0:
             return rnnt + ctc_weight * self._ctc_from_states(enc_state, labels, al, ll, reduction)
         return rnnt
+
+    @staticmethod
+    def _utterance_weights(w, B, reduction):
+        """the per-utterance weights of `loss` as the kernels read them: a detached, dense f32 [B] on the device"""
+        if reduction == "none":
+            raise ValueError("utterance_weights need reduction='mean' or 'sum' (per-utterance costs are not weighted)")
+        if not isinstance(w, torch.Tensor) or w.dtype not in (torch.float32, torch.float64) or tuple(w.shape) != (B,):
+            raise ValueError("utterance_weights must be an f32 / f64 tensor of shape [%d]" % B)
+        if not w.is_cuda:
+            raise ValueError("utterance_weights must live on the GPU (the MI355X build has no CPU path)")
+        return w.detach().to(torch.float32).contiguous()
 
     def _ctc_weight(self, ctc_weight):
         """the weight a call uses: None -> the config's; ValueError for a negative one, or a positive one on a module without the head"""
@@ -698,6 +733,111 @@ class Transducer(nn.Module):
         ops.weights_fresh()
         return _CTCHeadLossFn.apply(enc_state, self.ctc_head.weight, self.ctc_head.bias, labels, act_lens, label_lens, default_precision(),
                                     reduction, torch.is_grad_enabled(), 0)
+
+    def mwer_loss(self, inputs, inputs_length, targets, targets_length, *, beam_width=4, nbest=None, rnnt_weight=0.0, hypotheses=None,
+                  chunk=None, fastemit_lambda=0.0, details=False):
+        """Minimum word error rate training on the N-best list (Prabhavalkar et al. 2018; Guo et al. 2020 for RNN-T), on tokens: utterance b
+        has the distinct hypotheses y_1 .. y_n; c_i = the RNN-T lattice cost of (x_b, y_i), as loss(reduction='none') gives it;
+        P_i = softmax_i(-c_i) in float64; W_i = the edit distance of y_i to the transcript; E_b = sum_i P_i W_i.  Returns, as an f64 [1],
+            mean_b E_b + rnnt_weight * mean_b c(x_b, transcript_b)
+        whose gradient is that of sum_r w_r c_r over the rows r of the call with the CONSTANT weights w = -P_i (W_i - E_b) / B on a hypothesis
+        row (ttmi.metrics.mwer_weights) and rnnt_weight / B on a transcript row.
+
+        hypotheses=None: the N-best of `beam_decode_batch(beam_width, nbest)` on the detached audio states, under no_grad and in eval mode
+        (self.training is restored afterwards); else a list of token lists per utterance (ValueError for a duplicate within an utterance, an
+        utterance without a hypothesis, a token outside [0, V)).  An empty hypothesis ([]) is an ordinary row; an utterance with one
+        hypothesis adds its W_1 to the value and nothing to the gradient.
+
+        The audio encoder runs once, with gradient; its states are gathered per row (index_select: their gradients add back per utterance),
+        the label encoder runs on the row table (ragged: hypothesis rows b-major, then one transcript row per utterance when rnnt_weight > 0).
+        W comes from ttmi.metrics.edit_distance on the device.  Then two passes of the fused, chunked joint + loss over the same states:
+        pass 1 under no_grad gives c, pass 2 with utterance_weights = w forms the gradient - the [rows, T, U+1, V] logits never exist, one
+        chunk of `chunk` ROWS at a time (default: default_loss_chunk of the row count).  fastemit_lambda acts on pass 2's gradient.
+
+        details=True: -> (loss, MWERDetails(hypotheses, errors i32 [rows], posteriors f64 [rows], costs f32 [rows], expected_errors f64 [B]));
+        the per-row fields cover the whole row table: transcript rows carry errors 0 and posterior 0."""
+        from ttmi import metrics
+        fastemit_lambda = ops.check_fastemit(fastemit_lambda)
+        rnnt_weight = float(rnnt_weight)
+        if not rnnt_weight >= 0.0:
+            raise ValueError("mwer_loss: rnnt_weight must be >= 0, got %r" % (rnnt_weight,))
+        if not (inputs.is_cuda and targets.is_cuda):
+            raise ValueError("Transducer.mwer_loss: inputs and targets must live on the GPU (the MI355X build has no CPU path)")
+        dev, B, V = inputs.device, inputs.shape[0], self.config.vocab_size
+        enc_state = self.encoder(inputs, self._audio_mask(inputs))
+        if hypotheses is None:
+            was_training = self.training
+            self.eval()
+            try:
+                with torch.no_grad():
+                    nb = self.beam_decode_batch(enc_state.detach(), inputs_length, beam_width=beam_width, nbest=nbest)
+            finally:
+                self.train(was_training)
+            hypotheses = [[list(h.tokens) for h in res] for res in nb]
+        else:
+            hypotheses = [[[int(t) for t in h] for h in hs] for hs in hypotheses]
+            if len(hypotheses) != B:
+                raise ValueError("mwer_loss: %d hypothesis lists for %d utterances" % (len(hypotheses), B))
+        for b, hs in enumerate(hypotheses):
+            if not hs:
+                raise ValueError("mwer_loss: utterance %d has no hypothesis" % b)
+            if len({tuple(h) for h in hs}) != len(hs):
+                raise ValueError("mwer_loss: utterance %d holds the same hypothesis twice" % b)
+            if any(not 0 <= t < V for h in hs for t in h):
+                raise ValueError("mwer_loss: utterance %d has a token outside [0, %d)" % (b, V))
+        # the row table.  The label matrix is padded with 0 to the longest row and to ONE column at least: the loss kernels take a label
+        # pointer, which a [rows, 0] tensor does not have, so a call whose rows are all empty runs with U + 1 = 2 and label_lens = 0
+        # (hence check_lengths=False: max(label_lens) + 1 need not be U + 1 here, nor max(act_lens) T)
+        flat = [h for hs in hypotheses for h in hs]
+        n_hyp, n_max = len(flat), max(len(hs) for hs in hypotheses)
+        with_ref = rnnt_weight > 0.0
+        U = max([1] + [len(h) for h in flat] + ([targets.shape[1]] if with_ref else []))
+        host = np.zeros((n_hyp, U + 2), dtype=np.int64)                   # [labels | length | utterance]: one upload
+        k = 0
+        for b, hs in enumerate(hypotheses):
+            for h in hs:
+                host[k, :len(h)], host[k, U], host[k, U + 1] = h, len(h), b
+                k += 1
+        table = torch.from_numpy(host).to(dev)
+        labels, ll, row_utt = table[:, :U], table[:, U], table[:, U + 1]
+        tl = targets_length.to(device=dev, dtype=torch.long)
+        if with_ref:
+            tgt = F.pad(targets.long(), [0, U - targets.shape[1]])
+            tgt = tgt * (torch.arange(U, device=dev)[None, :] < tl[:, None])
+            labels, ll, row_all = torch.cat([labels, tgt]), torch.cat([ll, tl]), torch.cat([row_utt, torch.arange(B, device=dev)])
+        else:
+            row_all = row_utt
+        rows = labels.shape[0]
+        labels32, ll32 = labels.to(torch.int32).contiguous(), ll.to(torch.int32).contiguous()
+        errors = metrics.edit_distance(labels32, ll32, targets, tl, row_all).distance          # W, on the device: no host read
+        dec_rows = self._label_states(F.pad(labels, pad=[1, 0, 0, 0], value=0))
+        enc_rows = enc_state.index_select(0, row_all)
+        al32 = inputs_length.to(device=dev, dtype=torch.int32)[row_all].contiguous()
+        T, U1 = enc_rows.shape[1], dec_rows.shape[1]
+        ops.weights_fresh()
+        prec = default_precision()
+        chunk = self.default_loss_chunk(rows, T, U1) if chunk is None else int(chunk)
+        j = self.joint
+
+        def fused(reduction, grad, fe, w):
+            return _JointLossFn.apply(enc_rows, dec_rows, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
+                                      j.project_layer.bias, labels32, al32, ll32, prec, int(chunk), reduction, None, grad, 0, fe, w)
+        with torch.no_grad():
+            costs = fused("none", False, 0.0, None)                                               # pass 1
+        wt = metrics.mwer_weights(costs[:n_hyp], errors[:n_hyp], row_utt, B, max_per_utt=n_max)
+        value = wt.expected_errors.mean()
+        w, post = wt.weights, wt.posteriors
+        if with_ref:
+            value = value + rnnt_weight * costs[n_hyp:].double().mean()
+            w = torch.cat([w, torch.full((B,), rnnt_weight / B, dtype=torch.float64, device=dev)])
+            post = torch.cat([post, torch.zeros(B, dtype=torch.float64, device=dev)])
+        out = value.reshape(1)
+        if torch.is_grad_enabled():
+            weighted = fused("sum", True, fastemit_lambda, w.to(torch.float32).contiguous())      # pass 2: the value is `value`, the graph pass 2's
+            out = out + (weighted - weighted.detach()).double()
+        if details:
+            return out, MWERDetails(hypotheses, errors, post, costs, wt.expected_errors)
+        return out
 
     def ctc_loss(self, inputs, inputs_length, targets, targets_length, reduction="mean"):
         """CTC loss of the auxiliary head alone (blank = 0, the transducer's): the audio encoder, the head and ttmi.ctc's kernels.

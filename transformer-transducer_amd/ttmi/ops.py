@@ -965,3 +965,23 @@ def beam_step(logits, t, T_len, beam_in, beam_out, parent, fresh, blank=0):
     check(lib().ttmi_beam_step(_p(logits), c_int(_DT[logits.dtype]), c_long(logits.stride(-2)), c_int(B), c_int(W), c_int(V), c_int(blank), _p(t),
                                _p(T_len), _p(s0), _p(n0), _p(h0), _p(f0), _p(l0), _p(s1), _p(n1), _p(h1), _p(f1), _p(l1), c_long(h0.shape[2]),
                                c_long(f0.shape[2] if f0 is not None else 0), _p(parent), _p(fresh), _stream()), "ttmi_beam_step")
+
+
+# ----------------------------------------------------------------------------- error counting (ttmi.metrics)
+def edit_distance(hyp, hyp_len, ref, ref_len, ref_index=None):
+    """hyp i32 [P, Lh] / ref i32 [R, Lr] (last stride 1, any row pitch), hyp_len i32 [P], ref_len i32 [R], ref_index i32 [P] or None
+    -> out i32 [P, 4] = (distance, substitutions, deletions, insertions) per pair (include/ttmi.h: ttmi_edit_distance, the tie rule is
+    written there); device only, no synchronisation"""
+    _need_cuda(hyp, hyp_len, ref, ref_len, ref_index)
+    P, Lh = hyp.shape
+    R, Lr = ref.shape
+    for x, n in ((hyp_len, P), (ref_len, R)) + (((ref_index, P),) if ref_index is not None else ()):
+        assert x.dtype is torch.int32 and x.is_contiguous() and tuple(x.shape) == (n,)
+    for x in (hyp, ref):
+        assert x.dtype is torch.int32 and (x.shape[1] <= 1 or x.stride(1) == 1)
+    ld_hyp = hyp.stride(0) if P > 1 and Lh > 0 else Lh          # (the pitch of a single row, or of empty rows, is never used)
+    ld_ref = ref.stride(0) if R > 1 and Lr > 0 else Lr
+    out = torch.empty(P, 4, dtype=torch.int32, device=hyp.device)
+    check(lib().ttmi_edit_distance(_p(hyp), c_long(ld_hyp), _p(hyp_len), _p(ref), c_long(ld_ref), _p(ref_len), _p(ref_index), c_int(P), c_int(R),
+                                   c_int(Lh), c_int(Lr), _p(out), _stream()), "ttmi_edit_distance")
+    return out
