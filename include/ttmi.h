@@ -358,6 +358,45 @@ int ttmi_beam_step(const void* logits, int dtype, long ld, int B, int W, int V, 
                    const double* score_in, const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in,
                    double* score_out, int* len_out, long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det,
                    int* parent, int* fresh, void* stream);
+/* Contextual biasing (hotword boosting) inside the beam step: ttmi_beam_step_ctx is ttmi_beam_step with a deterministic weighted automaton
+ * over tokens steering the selection (ttmi.context.ContextGraph compiles one from hotword phrases; any automaton that meets the contract
+ * fits, a back-off n-gram table too).  Same launch shape and promises: one workgroup per utterance, no allocation, no host synchronisation,
+ * no memset node, capturable in a HIP graph, no floating-point atomics, two runs give the same bits.
+ * The automaton, device arrays: S >= 1 states, state 0 the root; A >= 0 arcs.  arc_off i32 [S + 1]; arc_sym / arc_next i32 [A], arc_w f32 [A]:
+ * the arcs of state s are entries arc_off[s] .. arc_off[s + 1] - 1, their symbols strictly ascending within a state and never the blank.
+ * fail i32 [S] with fail[s] < s for s > 0 (a failure chain ends at the root in at most S hops); fail_w f32 [S], fail_w[0] = the weight of a
+ * symbol without an arc at the root (it stays at the root).  All weights finite.  (A final weight per state is the host's business.)
+ * Transition step(s, k) -> (s', delta), delta accumulated in f64 in exactly this order:
+ *     acc = 0.0
+ *     loop: if s has an arc on k:  return (arc_next, acc + (double)arc_w)
+ *           if s == 0:             return (0, acc + (double)fail_w[0])
+ *           acc += (double)fail_w[s]; s = fail[s]
+ * State and accumulated bias are functions of the token sequence alone, so the two sides of a merge always carry the same state and the
+ * same bias bits: the merge rule needs no new case.
+ * Arguments: ttmi_beam_step's, then S, A and the six tables, then per slot state_in i32 [B, W] and bias_in f64 [B, W] with their _out twins
+ * in buffers of their own, then ws: ttmi_beam_ctx_ws_bytes(B, W, V) bytes of device memory the kernel may overwrite (B * W * V f64: per live
+ * slot the row of finished biases bias + delta(state, k) of every symbol k, written once per frame by the row's own wave, so that the
+ * candidate passes add one number per symbol and follow no chain).  It carries nothing from call to call.
+ * Rule = ttmi_beam_step's rule with these changes and no others:
+ *  - Every candidate has a score (unchanged: the model's log-probability, f64, merged by log-sum), a bias and a state.  The blank extension
+ *    of i: bias_i, state_i.  The extension of i by k: (state', delta) = step(state_i, k), bias' = bias_i + delta.
+ *  - key = score + bias', the f64 sum of the finished score and the finished bias; a NaN key counts as -inf.  The total order, the
+ *    per-parent preselection of the W best symbols and the rank counting use the key where ttmi_beam_step uses the score; the tie-break is
+ *    unchanged (parent ascending, blank before symbols, symbol ascending).  A candidate takes a slot only if its score > -inf and its key > -inf.
+ *  - A merged candidate takes i's state and bias; which side's details it takes is decided by the two SCORES, as in ttmi_beam_step.
+ *  - A state_in outside [0, S) is read as the root.  Whatever the tables hold, no index is followed outside them (an arc range is clamped
+ *    to [0, A], a failure link outside [0, S) reads as the root, a chain is left after S hops, an arc symbol outside [0, V) is ignored).
+ *  - A finished utterance (t[b] >= T_len[b]) copies state and bias through; an empty new slot gets state 0 and bias 0.
+ * score_out stays the model's log-probability.  With all weights zero every output ttmi_beam_step also has is bit-identical to its.
+ * rc < 0 with a ttmi_last_error text before any launch on a null pointer (the arc arrays may be null when A == 0), S < 1, A < 0, an _out
+ * buffer that is its _in buffer, or anything ttmi_beam_step refuses. */
+size_t ttmi_beam_ctx_ws_bytes(int B, int W, int V);
+int ttmi_beam_step_ctx(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len,
+                       const double* score_in, const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in,
+                       double* score_out, int* len_out, long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det,
+                       int* parent, int* fresh, int S, int A, const int* arc_off, const int* arc_sym, const int* arc_next, const float* arc_w,
+                       const int* fail, const float* fail_w, const int* state_in, const double* bias_in, int* state_out, double* bias_out,
+                       void* ws, void* stream);
 
 /* ---- error counting (ttmi.metrics: evaluation, and the per-hypothesis error counts of minimum word error rate training).
  * ttmi_edit_distance: token edit distance of P (hypothesis, transcript) pairs with its substitution / deletion / insertion counts.  One wave

@@ -3,11 +3,18 @@
 blank bias set for the emit rate - for beam widths 1, 4 and 8, beside greedy decode_batch (plain and details=True) measured in the same process
 on the same encoder states.  Utterances/s include the encoder's time, as bench_decode.py's do.  One JSON line.
 
-    python tools/bench_beam.py [--utts 8] [--T 500] [--emit-rate 0.1] [--precision fp32] [--widths 1,4,8]
+--context N adds contextual biasing: N phrases of 2 to 4 tokens are drawn from the greedy hypotheses of the run's own
+utterances, and per beam width three configurations are timed interleaved in this process, --repeats times each: no context (ttmi_beam_step),
+the phrases' graph with every weight 0 (ttmi_beam_step_ctx searching exactly the same hypotheses: the kernel's extra work alone) and the
+boosted graph.  Reported: median, min and max of the ms per frame, and the two kernels' own times by device events on the same beam and logits.
+
+    python tools/bench_beam.py [--utts 8] [--T 500] [--emit-rate 0.1] [--precision fp32] [--widths 1,4,8] [--context 100 [--boost 1.0] [--repeats 5]]
 """
 import argparse
 import json
 import os
+import random
+import statistics
 import sys
 import time
 
@@ -27,6 +34,67 @@ def timed(fn):
     return out, time.perf_counter() - t0
 
 
+def draw_phrases(hyps, n, seed=0):
+    """n phrases of 2 to 4 tokens cut from the hypotheses (token lists) at seeded random places"""
+    rng = random.Random(seed)
+    pool = [list(h) for h in hyps if len(h) >= 2]
+    if not pool:
+        raise SystemExit("--context: no hypothesis with two tokens to draw phrases from")
+    out = []
+    for _ in range(n):
+        h = rng.choice(pool)
+        length = rng.randint(2, min(4, len(h)))
+        start = rng.randrange(len(h) - length + 1)
+        out.append([int(k) for k in h[start:start + length]])
+    return out
+
+
+def kernel_times(W, V, B, graphs, frames=20, reps=50):
+    """device-event time of one ttmi_beam_step / ttmi_beam_step_ctx call, us, on a beam that `frames` steps on random logits have filled:
+    every kernel reads the same beam and the same logits, `reps` calls each, interleaved in rounds of 10"""
+    from ttmi import ops
+    dev = "cuda"
+    gen = torch.Generator(device=dev).manual_seed(0)
+    ld_hist, ld_det = frames + 3, frames + 2
+
+    def beam():
+        return (torch.full((B, W), -float("inf"), dtype=torch.float64, device=dev), torch.zeros(B, W, dtype=torch.int32, device=dev),
+                torch.zeros(B, W, ld_hist, dtype=torch.long, device=dev), torch.zeros(B, W, ld_det, dtype=torch.int32, device=dev),
+                torch.zeros(B, W, ld_det, dtype=torch.float32, device=dev))
+
+    def ctx():
+        return torch.zeros(B, W, dtype=torch.int32, device=dev), torch.zeros(B, W, dtype=torch.float64, device=dev)
+    cur, nxt, cur_x, nxt_x = beam(), beam(), ctx(), ctx()
+    cur[0][:, 0] = 0.0
+    t = torch.zeros(B, dtype=torch.int32, device=dev)
+    T_len = torch.full((B,), frames + 1, dtype=torch.int32, device=dev)
+    parent, fresh = torch.zeros(B, W, dtype=torch.int32, device=dev), torch.zeros(B, W, dtype=torch.int32, device=dev)
+    ws = ops.beam_ctx_workspace(B, W, V, dev)
+    zero = graphs["zero_weight"]
+    for _ in range(frames):                                              # fill the beam; the zero-weight graph keeps the states current
+        logits = 3.0 * torch.randn(B, W, V, device=dev, generator=gen)
+        ops.beam_step_ctx(logits, t, T_len, cur, nxt, parent, fresh, zero.tables, cur_x, nxt_x, ws)
+        t += 1
+        cur, nxt, cur_x, nxt_x = nxt, cur, nxt_x, cur_x
+    logits = 3.0 * torch.randn(B, W, V, device=dev, generator=gen)
+    calls = {"no_context": lambda: ops.beam_step(logits, t, T_len, cur, nxt, parent, fresh)}
+    for name, g in graphs.items():
+        calls[name] = lambda g=g: ops.beam_step_ctx(logits, t, T_len, cur, nxt, parent, fresh, g.tables, cur_x, nxt_x, ws)
+    times = {name: [] for name in calls}
+    for fn in calls.values():
+        fn()
+    for _ in range(reps // 10):
+        for name, fn in calls.items():
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(11)]
+            ev[0].record()
+            for i in range(10):
+                fn()
+                ev[i + 1].record()
+            torch.cuda.synchronize()
+            times[name] += [1e3 * a.elapsed_time(b) for a, b in zip(ev, ev[1:])]
+    return {name: {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2)} for name, v in times.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--utts", type=int, default=8)
@@ -34,6 +102,9 @@ def main():
     ap.add_argument("--emit-rate", type=float, default=0.1)
     ap.add_argument("--precision", default="fp32", choices=["bf16", "fp32"])
     ap.add_argument("--widths", default="1,4,8")
+    ap.add_argument("--context", type=int, default=0, help="number of hotword phrases drawn from the run's own hypotheses (0: no biasing runs)")
+    ap.add_argument("--boost", type=float, default=1.0)
+    ap.add_argument("--repeats", type=int, default=5)
     a = ap.parse_args()
     import bench_decode
     base, model, inputs, lens, hyps = bench_decode.run(a.utts, a.T, a.emit_rate, a.precision)       # builds the model, sets the blank bias, warms up
@@ -59,6 +130,32 @@ def main():
                                    "mean_best_score_per_frame": round(sum(r[0].score for r in res) / sum(lens), 4),
                                    "mean_greedy_score_per_frame": round(sum(g.score for g in greedy) / sum(lens), 4)}
         model.decoder.forward = decoder_forward
+        if a.context > 0:
+            from ttmi.context import ContextGraph
+            V = model.config.vocab_size
+            phrases = draw_phrases(hyps, a.context)
+            boosted = ContextGraph(phrases, boost=a.boost).validate(V).to(enc_states.device)
+            arc_off, arc_sym, arc_next, arc_w, fail, fail_w, final_w = boosted.cpu_tables()
+            zero = ContextGraph.from_tables(arc_off, arc_sym, arc_next, torch.zeros_like(arc_w), fail, torch.zeros_like(fail_w),
+                                            torch.zeros_like(final_w)).validate(V).to(enc_states.device)
+            configs = {"no_context": None, "zero_weight": zero, "boosted": boosted}
+            out["context"] = {"phrases": len(phrases), "states": boosted.S, "arcs": boosted.A, "boost": a.boost, "repeats": a.repeats, "widths": {}}
+            for W in [int(w) for w in a.widths.split(",")]:
+                res, times = {}, {name: [] for name in configs}
+                for name, g in configs.items():                                                     # warm-up of every configuration
+                    model.beam_decode_batch(enc_states, lens, beam_width=W, context=g)
+                for _ in range(a.repeats):
+                    for name, g in configs.items():
+                        res[name], dt = timed(lambda: model.beam_decode_batch(enc_states, lens, beam_width=W, context=g, return_bias=True))
+                        times[name].append(1e3 * dt / max(lens))
+                row = {name: {"ms_per_frame_median": round(statistics.median(v), 4), "ms_per_frame_min": round(min(v), 4),
+                              "ms_per_frame_max": round(max(v), 4)} for name, v in times.items()}
+                row["zero_weight_over_no_context"] = round(statistics.median(times["zero_weight"]) / statistics.median(times["no_context"]), 4)
+                row["zero_weight_equals_no_context"] = res["zero_weight"][0] == res["no_context"][0]
+                row["boosted_best_differs_in"] = sum(x[0].tokens != y[0].tokens for x, y in zip(res["boosted"][0], res["no_context"][0]))
+                row["boosted_mean_best_bias"] = round(sum(u[0] for u in res["boosted"][1]) / a.utts, 2)
+                row["kernel_us"] = kernel_times(W, V, a.utts, {"zero_weight": zero, "boosted": boosted})
+                out["context"]["widths"][str(W)] = row
     print(json.dumps(out), flush=True)
 
 

@@ -1676,6 +1676,18 @@ int ttmi_beam_step(const void* logits, int dtype, long ld, int B, int W, int V, 
     return beam_step(logits, dtype, ld, B, W, V, blank, t, T_len, score_in, len_in, hist_in, frames_in, tok_lp_in, score_out, len_out, hist_out,
                      frames_out, tok_lp_out, ld_hist, ld_det, parent, fresh, static_cast<hipStream_t>(stream));
 }
+// ... with contextual biasing (Transducer.beam_decode_batch(context=...), ttmi.h)
+size_t ttmi_beam_ctx_ws_bytes(int B, int W, int V) { return beam_ctx_ws_bytes(B, W, V); }
+int ttmi_beam_step_ctx(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len,
+                       const double* score_in, const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in,
+                       double* score_out, int* len_out, long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det,
+                       int* parent, int* fresh, int S, int A, const int* arc_off, const int* arc_sym, const int* arc_next, const float* arc_w,
+                       const int* fail, const float* fail_w, const int* state_in, const double* bias_in, int* state_out, double* bias_out,
+                       void* ws, void* stream) {
+    return beam_step_ctx(logits, dtype, ld, B, W, V, blank, t, T_len, score_in, len_in, hist_in, frames_in, tok_lp_in, score_out, len_out,
+                         hist_out, frames_out, tok_lp_out, ld_hist, ld_det, parent, fresh, S, A, arc_off, arc_sym, arc_next, arc_w, fail, fail_w,
+                         state_in, bias_in, state_out, bias_out, ws, static_cast<hipStream_t>(stream));
+}
 
 // ------------------------------------------------------------------ embedding (tt/decoder.py:26,39)
 int ttmi_embed_fwd(const long* tokens, const float* W, long n, int d, int V, float* out, void* stream) {

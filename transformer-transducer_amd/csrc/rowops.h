@@ -117,6 +117,14 @@ int greedy_advance_lp(unsigned long long* key, int B, int n, int n_hist, long* h
 int beam_step(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len, const double* score_in,
               const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in, double* score_out, int* len_out,
               long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det, int* parent, int* fresh, hipStream_t st);
+// the same frame with contextual biasing: a weighted automaton over tokens steers the selection (ttmi.h: ttmi_beam_step_ctx); ws holds
+// beam_ctx_ws_bytes(B, W, V) bytes
+size_t beam_ctx_ws_bytes(int B, int W, int V);
+int beam_step_ctx(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len, const double* score_in,
+                  const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in, double* score_out, int* len_out,
+                  long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det, int* parent, int* fresh, int S, int A,
+                  const int* arc_off, const int* arc_sym, const int* arc_next, const float* arc_w, const int* fail, const float* fail_w,
+                  const int* state_in, const double* bias_in, int* state_out, double* bias_out, void* ws, hipStream_t st);
 // batched transpose to bf16: for z = z1*nz2+z2, dst[z][c][r] = src[z1*s1 + z2*s2 + r*ld + c] (r < R, c < C), dst pitch ldd >= R with
 // zero fill in [R, ldd), dst slab = C*ldd.  src_dtype 0 = f32, 1 = bf16.  Produces the K-major operands of the position products.
 int transpose_bf16_batched(const void* src, int src_dtype, long ld, int nz1, int nz2, long s1, long s2, int R, int C, bf16_t* dst,

@@ -1621,7 +1621,20 @@ __global__ void greedy_advance_lp_kernel(unsigned long long* __restrict__ key, i
 //   4. rank counting over the W (W + 1) candidates: table index order IS (parent asc, blank first, symbols as picked), so a candidate's
 //      rank is the number of candidates with a larger score, or an equal one and a lower index.  No atomics on values: same bits every run;
 //   5. a wave per new slot copies tokens and details from its parent(s).
+//
+// beam_step_kernel<TL, true> is ttmi_beam_step_ctx: the same walk with a bias and an automaton state per slot (the rule: ttmi.h).  What differs:
+//   2. before its candidate passes the row's wave writes the row of finished biases bias_w + delta(state_w, v), v in [0, V), into the
+//      workspace (beam_ctx_fill below), so a pass adds one f64 per symbol and follows no chain; the preselection's key is score + bias';
+//   3. / 4. the blank candidate's key is its finished (merged) score + bias_i; ranks are counted on the keys;
+//   5. lane 0 of the new slot's wave takes step(state_i, k) once more for the winner, by binary search: the same sums in the same order as the
+//      workspace row's, so bias_out is the bias its key was formed with.
 constexpr int BEAM_MAX_W = 32;
+struct BeamCtxArgs {
+    int S, A;
+    const int *arc_off, *arc_sym, *arc_next; const float* arc_w; const int* fail; const float* fail_w;
+    const int* state_in; const double* bias_in; int* state_out; double* bias_out;
+    double* ws;                                              // [B, W, V]: a row of finished biases per live slot, rewritten every frame
+};
 struct BeamStepArgs {
     const void* logits; long ld; int W, V, blank;
     const int *t, *T_len;
@@ -1629,8 +1642,69 @@ struct BeamStepArgs {
     double* score_out; int* len_out; long* hist_out; int* frames_out; float* tok_lp_out;
     long ld_hist, ld_det;
     int *parent, *fresh;
+    BeamCtxArgs x;                                           // read by the biased instantiation only
 };
 __device__ __forceinline__ double beam_key(double s) { return s > -INFINITY ? s : -INFINITY; }      // NaN ranks as -inf
+// ---- contextual biasing (ttmi_beam_step_ctx; the automaton's contract and step(s, k) are ttmi.h's).  No index is followed outside the tables,
+// whatever they hold: a state or a failure link outside [0, S) reads as the root, arc ranges are clamped to [0, A], a chain ends after S hops.
+constexpr int BEAM_CTX_CHAIN = 16;                           // chain levels a wave keeps in LDS; deeper ones are walked to again
+__device__ __forceinline__ int beam_ctx_state(const BeamCtxArgs& x, int s) { return (s >= 0 && s < x.S) ? s : 0; }
+__device__ __forceinline__ void beam_ctx_arcs(const BeamCtxArgs& x, int s, int& lo, int& hi) {
+    lo = min(max(x.arc_off[s], 0), x.A);
+    hi = min(max(x.arc_off[s + 1], lo), x.A);
+}
+// one hop of the chain: level L -> L + 1; false at the chain's last level (the root, or S hops done)
+__device__ __forceinline__ bool beam_ctx_hop(const BeamCtxArgs& x, int& s, double& acc, int level) {
+    if (s == 0 || level >= x.S) return false;
+    acc += (double)x.fail_w[s];
+    s = beam_ctx_state(x, x.fail[s]);
+    return true;
+}
+// step(s, k) as ttmi.h writes it, by one thread: a binary search per level
+__device__ void beam_ctx_step(const BeamCtxArgs& x, int s, int k, int& next, double& delta) {
+    double acc = 0.0;
+    for (int level = 0;; ++level) {
+        int lo, hi;
+        beam_ctx_arcs(x, s, lo, hi);
+        while (lo < hi) {
+            const int mid = lo + ((hi - lo) >> 1), sym = x.arc_sym[mid];
+            if (sym == k) { next = x.arc_next[mid]; delta = acc + (double)x.arc_w[mid]; return; }
+            if (sym < k) lo = mid + 1;
+            else hi = mid;
+        }
+        if (!beam_ctx_hop(x, s, acc, level)) { next = 0; delta = acc + (double)x.fail_w[0]; return; }
+    }
+}
+// this wave's stores so far are in memory before anything it issues next (a level's stores before the next level's, the row before its reads)
+__device__ __forceinline__ void beam_ctx_drain() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+// the row of finished biases bias_i + delta(s0, v), v in [0, V), by the row's own wave: almost every symbol shares the default (the chain's
+// summed fail_w down to the root, plus fail_w[0]); the row is filled with it and then overwritten with the arcs of the chain's states from the
+// root end upwards, so the first arc on the chain wins.  `ch_s` / `ch_acc`: this wave's BEAM_CTX_CHAIN LDS entries.
+__device__ void beam_ctx_fill(const BeamCtxArgs& x, int s0, double bias, double* row, int V, int* ch_s, double* ch_acc, int lane) {
+    int s = s0, D = 0;
+    double acc = 0.0;
+    do {
+        if (D < BEAM_CTX_CHAIN) { ch_s[D] = s; ch_acc[D] = acc; }      // (every lane writes the same value)
+    } while (beam_ctx_hop(x, s, acc, D++));
+    const double dflt = bias + (acc + (double)x.fail_w[0]);
+    for (int v = lane; v < V; v += 64) row[v] = dflt;
+    for (int L = D - 1; L >= 0; --L) {
+        beam_ctx_drain();
+        const int from = min(L, BEAM_CTX_CHAIN - 1);
+        s = ch_s[from]; acc = ch_acc[from];
+        for (int l = from; l < L; ++l) beam_ctx_hop(x, s, acc, l);
+        int lo, hi;
+        beam_ctx_arcs(x, s, lo, hi);
+        for (int q = lo + lane; q < hi; q += 64) {
+            const int sym = x.arc_sym[q];
+            if (sym >= 0 && sym < V) row[sym] = bias + (acc + (double)x.arc_w[q]);
+        }
+    }
+    beam_ctx_drain();
+}
 template <typename TL>
 __device__ __forceinline__ float beam_load(const TL* p) {
     if constexpr (sizeof(TL) == 4) return *p;
@@ -1651,13 +1725,17 @@ __device__ __forceinline__ void beam_copy_slot(const BeamStepArgs& a, long base,
     for (int c = lane; c < n_det && c < a.ld_det; c += 64) { fo[c] = fi[c]; lo[c] = li[c]; }
     if (app_det && lane == 0 && n_det < a.ld_det) { fo[n_det] = app_frame; lo[n_det] = app_lp; }
 }
-template <typename TL>
+template <typename TL, bool CTX>
 __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
     constexpr int MW = BEAM_MAX_W, NC = MW * (MW + 1);
     __shared__ double s_score[MW], c_score[NC];
     __shared__ float s_lse[MW], c_lp[NC], s_mlp[MW];
     __shared__ int s_len[MW], s_partner[MW], s_msym[MW], c_sym[NC], s_win[MW];
     __shared__ long s_last[MW];
+    // the biased instantiation ranks by c_key = score + bias; without a context the key IS the score
+    __shared__ double c_keys[CTX ? NC : 1], s_bias[CTX ? MW : 1], ch_acc[CTX ? 4 * BEAM_CTX_CHAIN : 1];
+    __shared__ int s_state[CTX ? MW : 1], ch_s[CTX ? 4 * BEAM_CTX_CHAIN : 1];
+    double* const c_key = CTX ? c_keys : c_score;
     const int b = blockIdx.x, W = a.W, V = a.V, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nc = W * (W + 1);
     const long base = (long)b * W;
     const int tb = a.t[b];
@@ -1670,6 +1748,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
                 a.len_out[base + w] = a.len_in[base + w];
                 a.parent[base + w] = w;
                 a.fresh[base + w] = 0;
+                if constexpr (CTX) { a.x.state_out[base + w] = a.x.state_in[base + w]; a.x.bias_out[base + w] = a.x.bias_in[base + w]; }
             }
         }
         return;
@@ -1685,8 +1764,15 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
         s_msym[tid] = -1;
         s_lse[tid] = NAN;
         s_win[tid] = -1;
+        if constexpr (CTX) {
+            s_state[tid] = live ? beam_ctx_state(a.x, a.x.state_in[base + tid]) : 0;
+            s_bias[tid] = live ? a.x.bias_in[base + tid] : 0.0;
+        }
     }
-    for (int c = tid; c < nc; c += 256) { c_score[c] = -INFINITY; c_sym[c] = -1; c_lp[c] = 0.f; }
+    for (int c = tid; c < nc; c += 256) {
+        c_score[c] = -INFINITY; c_sym[c] = -1; c_lp[c] = 0.f;
+        if constexpr (CTX) c_key[c] = -INFINITY;
+    }
     __syncthreads();
     // 1. merge partners
     for (int p = tid; p < W * W; p += 256) {
@@ -1725,6 +1811,12 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
         const float lse = __shfl(m + logf(s), 0, 64);        // ONE value for the row: the lanes' copies of (m, s) may differ in the last ulp
         if (!(lse - lse == 0.f)) continue;                   // a NaN, a +inf or nothing but -inf in the row: every candidate of it scores NaN
         if (lane == 0) s_lse[w] = lse;
+        const double* bp = nullptr;                          // the row's finished biases
+        if constexpr (CTX) {
+            double* row = a.x.ws + (base + w) * V;
+            beam_ctx_fill(a.x, s_state[w], s_bias[w], row, V, ch_s + wave * BEAM_CTX_CHAIN, ch_acc + wave * BEAM_CTX_CHAIN, lane);
+            bp = row;
+        }
         double ps = INFINITY;                                // the previous pick: candidates after it in (score desc, symbol asc) remain
         int pk = -1, cnt = 0;
         while (cnt < W) {
@@ -1734,7 +1826,8 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
             for (int v = lane; v < V; v += 64) {
                 if (v == a.blank) continue;
                 const float l = beam_load(p + v) - lse;
-                const double sc = beam_key(sw + (double)l);
+                double sc = beam_key(sw + (double)l);
+                if constexpr (CTX) sc = beam_key(sc + bp[v]);
                 if ((sc < ps || (sc == ps && v > pk)) && (sc > bs || (sc == bs && v < bk))) { bs = sc; bk = v; bl = l; }
             }
 #pragma unroll
@@ -1751,7 +1844,9 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
             if (merged) continue;
             if (lane == 0) {
                 const int c = w * (W + 1) + 1 + cnt;
-                c_score[c] = bs; c_sym[c] = bk; c_lp[c] = bl;
+                if constexpr (CTX) { c_key[c] = bs; c_score[c] = beam_key(sw + (double)bl); }
+                else c_score[c] = bs;
+                c_sym[c] = bk; c_lp[c] = bl;
             }
             ++cnt;
         }
@@ -1775,6 +1870,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
             }
         }
         c_score[i * (W + 1)] = sc;
+        if constexpr (CTX) c_key[i * (W + 1)] = beam_key(sc + s_bias[i]);
         c_sym[i * (W + 1)] = -1 - from_symbol;               // -1: blank; -2: blank with the details of the merged symbol extension
     } else if (tid < W && s_score[tid] > -INFINITY) {
         // this row has no finite log-sum-exp, but a partner's symbol extension still spells this slot's tokens
@@ -1783,18 +1879,19 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
             const TL* pj = static_cast<const TL*>(a.logits) + (base + j) * a.ld;
             const float l = beam_load(pj + s_msym[i]) - s_lse[j];
             c_score[i * (W + 1)] = beam_key(s_score[j] + (double)l);
+            if constexpr (CTX) c_key[i * (W + 1)] = beam_key(c_score[i * (W + 1)] + s_bias[i]);
             c_sym[i * (W + 1)] = -2;
             s_mlp[i] = l;
         }
     }
     __syncthreads();
-    // 4. rank counting
+    // 4. rank counting (a key > -inf has a score > -inf: a score of -inf gives a key of -inf or NaN)
     for (int c = tid; c < nc; c += 256) {
-        const double sc = c_score[c];
+        const double sc = c_key[c];
         if (!(sc > -INFINITY)) continue;
         int rank = 0;
         for (int o = 0; o < nc; ++o) {
-            const double so = c_score[o];
+            const double so = c_key[o];
             rank += (so > sc) | ((so == sc) & (o < c));
         }
         if (rank < W) s_win[rank] = c;
@@ -1804,7 +1901,10 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
     for (int r = wave; r < W; r += 4) {
         const int c = s_win[r];
         if (c < 0) {                                         // fewer candidates with a probability than slots: an empty slot
-            if (lane == 0) { a.score_out[base + r] = -INFINITY; a.len_out[base + r] = 0; a.parent[base + r] = r; a.fresh[base + r] = 0; }
+            if (lane == 0) {
+                a.score_out[base + r] = -INFINITY; a.len_out[base + r] = 0; a.parent[base + r] = r; a.fresh[base + r] = 0;
+                if constexpr (CTX) { a.x.state_out[base + r] = 0; a.x.bias_out[base + r] = 0.0; }
+            }
             continue;
         }
         const int i = c / (W + 1), sym = c_sym[c], n = s_len[i];
@@ -1816,6 +1916,13 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
             a.len_out[base + r] = sym >= 0 ? n + 1 : n;
             a.parent[base + r] = i;
             a.fresh[base + r] = sym >= 0;
+            if constexpr (CTX) {
+                int next = s_state[i];
+                double delta = 0.0;
+                if (sym >= 0) beam_ctx_step(a.x, s_state[i], sym, next, delta);
+                a.x.state_out[base + r] = next;
+                a.x.bias_out[base + r] = sym >= 0 ? s_bias[i] + delta : s_bias[i];
+            }
         }
     }
 }
@@ -1835,10 +1942,42 @@ int beam_step(const void* logits, int dtype, long ld, int B, int W, int V, int b
     TTMI_REQUIRE(score_in != score_out && len_in != len_out && hist_in != hist_out && (n_det == 0 || (frames_in != frames_out && tok_lp_in != tok_lp_out)),
                  "beam_step: the new beam needs buffers of its own");
     BeamStepArgs a{logits, ld, W, V, blank, t, T_len, score_in, len_in, hist_in, frames_in, tok_lp_in, score_out, len_out, hist_out, frames_out,
-                   tok_lp_out, ld_hist, ld_det, parent, fresh};
-    if (dtype == 0) hipLaunchKernelGGL(beam_step_kernel<float>, dim3(B), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(beam_step_kernel<bf16_t>, dim3(B), dim3(256), 0, st, a);
+                   tok_lp_out, ld_hist, ld_det, parent, fresh, BeamCtxArgs{}};
+    if (dtype == 0) hipLaunchKernelGGL((beam_step_kernel<float, false>), dim3(B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((beam_step_kernel<bf16_t, false>), dim3(B), dim3(256), 0, st, a);
     TTMI_LAUNCH_CHECK("beam_step_kernel");
+    return TTMI_OK;
+}
+
+size_t beam_ctx_ws_bytes(int B, int W, int V) {
+    return (B > 0 && W > 0 && V > 0) ? (size_t)B * (size_t)W * (size_t)V * sizeof(double) : 0;
+}
+
+int beam_step_ctx(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len, const double* score_in,
+                  const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in, double* score_out, int* len_out,
+                  long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det, int* parent, int* fresh, int S, int A,
+                  const int* arc_off, const int* arc_sym, const int* arc_next, const float* arc_w, const int* fail, const float* fail_w,
+                  const int* state_in, const double* bias_in, int* state_out, double* bias_out, void* ws, hipStream_t st) {
+    TTMI_REQUIRE(logits && t && T_len && score_in && len_in && hist_in && score_out && len_out && hist_out && parent && fresh,
+                 "beam_step_ctx: null pointer");
+    TTMI_REQUIRE(arc_off && fail && fail_w && state_in && bias_in && state_out && bias_out && ws, "beam_step_ctx: null pointer");
+    TTMI_REQUIRE(S >= 1 && A >= 0, "beam_step_ctx: an automaton has at least its root and no negative arc count, got S = %d, A = %d", S, A);
+    TTMI_REQUIRE(A == 0 || (arc_sym && arc_next && arc_w), "beam_step_ctx: null pointer (arc tables)");
+    const int n_det = !!frames_in + !!tok_lp_in + !!frames_out + !!tok_lp_out;
+    TTMI_REQUIRE(n_det == 0 || n_det == 4, "beam_step_ctx: frames / tok_lp come as all four arrays or none");
+    TTMI_REQUIRE(dtype == 0 || dtype == 1, "beam_step_ctx: logits are f32 (0) or bf16 (1)");
+    TTMI_REQUIRE(W >= 1 && W <= BEAM_MAX_W, "beam_step_ctx: beam width %d outside [1, %d]", W, BEAM_MAX_W);
+    TTMI_REQUIRE(B > 0 && V >= 2 && ld >= V && blank >= 0 && blank < V && ld_hist >= 2 && (n_det == 0 || ld_det >= 1),
+                 "beam_step_ctx: bad arguments");
+    TTMI_REQUIRE(score_in != score_out && len_in != len_out && hist_in != hist_out && (n_det == 0 || (frames_in != frames_out && tok_lp_in != tok_lp_out)) &&
+                     state_in != state_out && bias_in != bias_out,
+                 "beam_step_ctx: the new beam needs buffers of its own");
+    BeamStepArgs a{logits, ld, W, V, blank, t, T_len, score_in, len_in, hist_in, frames_in, tok_lp_in, score_out, len_out, hist_out, frames_out,
+                   tok_lp_out, ld_hist, ld_det, parent, fresh,
+                   BeamCtxArgs{S, A, arc_off, arc_sym, arc_next, arc_w, fail, fail_w, state_in, bias_in, state_out, bias_out, static_cast<double*>(ws)}};
+    if (dtype == 0) hipLaunchKernelGGL((beam_step_kernel<float, true>), dim3(B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((beam_step_kernel<bf16_t, true>), dim3(B), dim3(256), 0, st, a);
+    TTMI_LAUNCH_CHECK("beam_step_ctx_kernel");
     return TTMI_OK;
 }
 

@@ -1166,7 +1166,7 @@ class Transducer(nn.Module):
         return [self.decode(enc_states[b], inputs_length[b]) for b in range(inputs.size(0))]
 
     @torch.no_grad()
-    def beam_decode_batch(self, enc_states, lengths, beam_width=4, nbest=None):
+    def beam_decode_batch(self, enc_states, lengths, beam_width=4, nbest=None, context=None, return_bias=False):
         """Frame-synchronous beam search of EVERY utterance of a batch at once -> per utterance a list of at most `nbest` (default: beam_width)
         DecodeResult, best first.  The probability model is the greedy decoder's (`decode_batch`): each of an utterance's T_b frames takes one
         decision, blank or one symbol, against the label state of the tokens so far, and the emitting frame is consumed.  Unlike `beam_search`
@@ -1178,6 +1178,12 @@ class Transducer(nn.Module):
         (one workgroup per utterance), ONE host read brings the new slots' lengths and which of them are new sequences, and the label encoder
         runs on those only, one call per distinct history length (the relative-position term depends on the sequence length, see
         `decode_batch`); every other slot takes its parent's state by a gather on the device.  Finished utterances pass through unchanged.
+        context = a ttmi.context.ContextGraph (hotword boosting): the same loop, but every slot also carries the automaton's state and its
+        accumulated bias, and ttmi_beam_step_ctx selects by score + bias (include/ttmi.h has the rule), so a hotword whose first token ranks
+        below the beam width on its score alone can stay in the beam.  After the last frame final_bias = bias + final_w[state] (a hotword
+        begun and not finished keeps nothing) and the list is ordered by score + final_bias, descending, the slot ascending on ties, then cut
+        to `nbest`.  `score` stays the model's log-probability (comparable with greedy scores, usable by mwer_loss).  return_bias=True ->
+        (results, biases): biases[b][n] = the final bias of results[b][n], 0.0 without a context.  context=None runs ttmi_beam_step as before.
         Not built: a cache of label states for sequences seen on earlier frames, a captured graph of the loop, a streaming variant."""
         if not enc_states.is_cuda:
             raise ValueError("beam_decode_batch: enc_states must live on the GPU (the MI355X build has no CPU path)")
@@ -1203,13 +1209,22 @@ class Transducer(nn.Module):
             return bm["score"], bm["meta"][0], bm["hist"], bm["frames"], bm["tok_lp"]
         cur, nxt = beam(), beam()
         cur["score"][:, 0] = 0.0                                     # slot 0 holds the start symbol, the other slots are empty
+        if context is not None:
+            context.validate(self.config.vocab_size).to(dev)
+            for bm in (cur, nxt):
+                bm["ctx"] = (torch.zeros(B, W, dtype=torch.int32, device=dev), torch.zeros(B, W, dtype=torch.float64, device=dev))
+            ctx_ws = ops.beam_ctx_workspace(B, W, self.config.vocab_size, dev)
         parent = torch.zeros(B, W, dtype=torch.int32, device=dev)
         start = self.decoder(torch.zeros(1, 1, dtype=torch.long, device=dev))[:, -1, :]
         states = start[None].expand(B, W, -1).contiguous()           # [B, W, d]; what an empty slot holds is never read by the kernel
         d = states.shape[-1]
         for f in range(T_max):
             logits = self.joint(enc_states[:, f:f + 1].contiguous(), states)                      # [B, 1, W, V]
-            ops.beam_step(logits[:, 0], t, T_len, arrays(cur), arrays(nxt), parent, nxt["meta"][1], blank=0)
+            if context is None:
+                ops.beam_step(logits[:, 0], t, T_len, arrays(cur), arrays(nxt), parent, nxt["meta"][1], blank=0)
+            else:
+                ops.beam_step_ctx(logits[:, 0], t, T_len, arrays(cur), arrays(nxt), parent, nxt["meta"][1], context.tables, cur["ctx"],
+                                  nxt["ctx"], ctx_ws, blank=0)
             t += 1
             cur, nxt = nxt, cur
             if f == T_max - 1:
@@ -1229,29 +1244,35 @@ class Transducer(nn.Module):
                 states.view(B * W, d).index_copy_(0, rows, self.decoder(hist.contiguous())[:, -1, :])
         # ONE transfer, as f64 (exact for token ids, counts, frames and f32 log-probabilities): score | len | tokens | frames | logprobs
         packed = torch.cat([cur["score"][:, :, None], cur["meta"][0].double()[:, :, None], cur["hist"][:, :, 1:].double(), cur["frames"].double(),
-                            cur["tok_lp"].double()], dim=2).cpu()
-        out = []
+                            cur["tok_lp"].double()] +
+                           ([] if context is None else [(cur["ctx"][1] + context.final_w[cur["ctx"][0].long()].double())[:, :, None]]), dim=2).cpu()
+        out, biases = [], []
         for b in range(B):
-            res = []
+            res, bias = [], []
             for w in range(W):
                 score, c = float(packed[b, w, 0]), int(packed[b, w, 1])
                 if not score > -math.inf:                            # an empty slot
                     continue
                 tok, frm, lpr = (packed[b, w, 2 + i * ld_det:2 + i * ld_det + c].tolist() for i in range(3))
                 res.append(DecodeResult([int(v) for v in tok], [int(v) for v in frm], lpr, score))
+                bias.append(0.0 if context is None else float(packed[b, w, -1]))
+            if context is not None:                                  # the slots are in key order with the running bias; the final bias reorders
+                order = sorted(range(len(res)), key=lambda n: (-(res[n].score + bias[n]), n))
+                res, bias = [res[n] for n in order], [bias[n] for n in order]
             if not res or not math.isfinite(res[0].score):
                 raise RuntimeError("beam search: utterance %d has no hypothesis with a finite score (NaN logits?)" % b)
             out.append(res[:nbest])
-        return out
+            biases.append(bias[:nbest])
+        return (out, biases) if return_bias else out
 
     @torch.no_grad()
-    def recognize_nbest(self, inputs, inputs_length=None, audio_mask=None, beam_width=4, nbest=None):
+    def recognize_nbest(self, inputs, inputs_length=None, audio_mask=None, beam_width=4, nbest=None, context=None, return_bias=False):
         """N-best recognition of a batch: the encoder, then `beam_decode_batch` -> per utterance a list of at most `nbest` (default:
-        beam_width) DecodeResult, best first, with merged, comparable scores"""
+        beam_width) DecodeResult, best first, with merged, comparable scores; `context` / `return_bias`: contextual biasing, see there"""
         if not inputs.is_cuda:
             raise ValueError("recognize_nbest: inputs must live on the GPU (the MI355X build has no CPU path)")
         enc_states = self.encoder(inputs, audio_mask)
-        return self.beam_decode_batch(enc_states, inputs_length, beam_width=beam_width, nbest=nbest)
+        return self.beam_decode_batch(enc_states, inputs_length, beam_width=beam_width, nbest=nbest, context=context, return_bias=return_bias)
 
     @torch.no_grad()
     def beam_search(self, enc_state, lengths, beam_width=5, block=64):
