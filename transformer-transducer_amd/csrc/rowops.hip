@@ -17,6 +17,38 @@ constexpr int WPB = 4;   // waves per block for the wave-per-row kernels
 __device__ __forceinline__ long wave_row() { return (long)blockIdx.x * WPB + (threadIdx.x >> 6); }
 
 // ------------------------------------------------------------------ LayerNorm
+// The register-resident LayerNorm kernels restate one another's arithmetic - the in-pass second norm of ln_fwd_row_kernel is ln_fwd_row_kernel
+// on the row it has just produced, ln_bwd_pair_kernel is two ln_bwd_fused_kernel passes - and the layer-level entries promise the sub-layer
+// calls' results (tests/test_layer_calls_gpu.py).  Which multiply-adds are fused is therefore WRITTEN here and contraction is off: left
+// to the compiler, the <1> instances fused other pairs than their counterparts (an f32 ulp per element, hence bf16 operands that differ).
+__device__ __forceinline__ float ln_sum4(const float v[4]) {
+#pragma clang fp contract(off)
+    return (v[0] + v[1]) + (v[2] + v[3]);
+}
+__device__ __forceinline__ float ln_sq4(const float v[4], float mean) {
+#pragma clang fp contract(off)
+    const float a = v[0] - mean, b = v[1] - mean, c = v[2] - mean, e = v[3] - mean;
+    return __builtin_fmaf(a, a, b * b) + __builtin_fmaf(c, c, e * e);
+}
+__device__ __forceinline__ float ln_affine(float v, float mean, float rstd, float g, float b) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf((v - mean) * rstd, g, b);
+}
+// one element of a LayerNorm backward row: the row sums' terms and the gamma / beta partial sums
+__device__ __forceinline__ void ln_bwd_terms(float v, float gam, float xh, float& m1, float& m2, float& ag, float& ab) {
+#pragma clang fp contract(off)
+    const float dxh = v * gam;
+    m1 += dxh;
+    m2 = __builtin_fmaf(dxh, xh, m2);
+    ag = __builtin_fmaf(v, xh, ag);
+    ab += v;
+}
+// rs (v gam - m1 - xh m2), without the factor rs
+__device__ __forceinline__ float ln_bwd_inner(float v, float gam, float xh, float m1, float m2) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(-xh, m2, __builtin_fmaf(v, gam, -m1));
+}
+
 __global__ __launch_bounds__(WPB * 64) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ res,
                                                           const float* __restrict__ g, const float* __restrict__ b, long rows,
                                                           int d, float eps, float* __restrict__ s_out, float* __restrict__ y,
@@ -150,7 +182,7 @@ __global__ __launch_bounds__(WPB * 64) void ln_fwd_row_kernel(const float* __res
                 v[k][0] += w.x * m[0]; v[k][1] += w.y * m[1]; v[k][2] += w.z * m[2]; v[k][3] += w.w * m[3];
             }
             if (s_out) *reinterpret_cast<float4*>(s_out + base + c0) = make_float4(v[k][0], v[k][1], v[k][2], v[k][3]);
-            sum += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
+            sum += ln_sum4(v[k]);
         } else {
             v[k][0] = v[k][1] = v[k][2] = v[k][3] = 0.f;
         }
@@ -160,10 +192,7 @@ __global__ __launch_bounds__(WPB * 64) void ln_fwd_row_kernel(const float* __res
     float sq = 0.f;
 #pragma unroll
     for (int k = 0; k < KV; ++k)
-        if (k * 256 + lane * 4 < d) {
-            const float a = v[k][0] - mean, bq = v[k][1] - mean, c = v[k][2] - mean, e = v[k][3] - mean;
-            sq += (a * a + bq * bq) + (c * c + e * e);
-        }
+        if (k * 256 + lane * 4 < d) sq += ln_sq4(v[k], mean);
     const float rstd = rsqrtf(wave_sum(sq) * invd + eps);
     if (lane == 0) {
         if (mean_o) mean_o[r] = mean;
@@ -178,10 +207,10 @@ __global__ __launch_bounds__(WPB * 64) void ln_fwd_row_kernel(const float* __res
             const float4 bb = *reinterpret_cast<const float4*>(b + c0);
             float m[4];
             drop_mult4(odrop, base + c0, m);
-            v[k][0] = ((v[k][0] - mean) * rstd * gg.x + bb.x) * m[0];
-            v[k][1] = ((v[k][1] - mean) * rstd * gg.y + bb.y) * m[1];
-            v[k][2] = ((v[k][2] - mean) * rstd * gg.z + bb.z) * m[2];
-            v[k][3] = ((v[k][3] - mean) * rstd * gg.w + bb.w) * m[3];
+            v[k][0] = ln_affine(v[k][0], mean, rstd, gg.x, bb.x) * m[0];
+            v[k][1] = ln_affine(v[k][1], mean, rstd, gg.y, bb.y) * m[1];
+            v[k][2] = ln_affine(v[k][2], mean, rstd, gg.z, bb.z) * m[2];
+            v[k][3] = ln_affine(v[k][3], mean, rstd, gg.w, bb.w) * m[3];
             if (y) *reinterpret_cast<float4*>(y + base + c0) = make_float4(v[k][0], v[k][1], v[k][2], v[k][3]);
             if (y16) {
                 uint2 w;
@@ -189,7 +218,7 @@ __global__ __launch_bounds__(WPB * 64) void ln_fwd_row_kernel(const float* __res
                 w.y = pack_bf16x2(v[k][2], v[k][3]);
                 *reinterpret_cast<uint2*>(y16 + base + c0) = w;
             }
-            sum2 += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
+            sum2 += ln_sum4(v[k]);
         }
     }
     if (!g2) return;                                                   // kernel argument: wave-uniform
@@ -197,10 +226,7 @@ __global__ __launch_bounds__(WPB * 64) void ln_fwd_row_kernel(const float* __res
     float sq2 = 0.f;
 #pragma unroll
     for (int k = 0; k < KV; ++k)
-        if (k * 256 + lane * 4 < d) {
-            const float a = v[k][0] - mean2, bq = v[k][1] - mean2, c = v[k][2] - mean2, e = v[k][3] - mean2;
-            sq2 += (a * a + bq * bq) + (c * c + e * e);
-        }
+        if (k * 256 + lane * 4 < d) sq2 += ln_sq4(v[k], mean2);
     const float rstd2 = rsqrtf(wave_sum(sq2) * invd + eps);
     if (lane == 0) {
         mean2_o[r] = mean2;
@@ -213,8 +239,8 @@ __global__ __launch_bounds__(WPB * 64) void ln_fwd_row_kernel(const float* __res
             const float4 gg = *reinterpret_cast<const float4*>(g2 + c0);
             const float4 bb = *reinterpret_cast<const float4*>(b2 + c0);
             uint2 w;
-            w.x = pack_bf16x2((v[k][0] - mean2) * rstd2 * gg.x + bb.x, (v[k][1] - mean2) * rstd2 * gg.y + bb.y);
-            w.y = pack_bf16x2((v[k][2] - mean2) * rstd2 * gg.z + bb.z, (v[k][3] - mean2) * rstd2 * gg.w + bb.w);
+            w.x = pack_bf16x2(ln_affine(v[k][0], mean2, rstd2, gg.x, bb.x), ln_affine(v[k][1], mean2, rstd2, gg.y, bb.y));
+            w.y = pack_bf16x2(ln_affine(v[k][2], mean2, rstd2, gg.z, bb.z), ln_affine(v[k][3], mean2, rstd2, gg.w, bb.w));
             *reinterpret_cast<uint2*>(h16 + base + c0) = w;
         }
     }
@@ -337,11 +363,7 @@ __global__ __launch_bounds__(256) void ln_bwd_fused_kernel(const float* __restri
                 for (int c = 0; c < 4; ++c) {
                     v[k][c] = av[c] * dm[c];
                     xh[k][c] = (bv[c] - mu) * rs;
-                    const float dxh = v[k][c] * gam[k][c];
-                    m1 += dxh;
-                    m2 += dxh * xh[k][c];
-                    ag[k][c] += v[k][c] * xh[k][c];
-                    ab[k][c] += v[k][c];
+                    ln_bwd_terms(v[k][c], gam[k][c], xh[k][c], m1, m2, ag[k][c], ab[k][c]);
                 }
             } else {
 #pragma unroll
@@ -356,10 +378,14 @@ __global__ __launch_bounds__(256) void ln_bwd_fused_kernel(const float* __restri
             if (c0 < d) {
                 float o[4];
 #pragma unroll
-                for (int c = 0; c < 4; ++c) o[c] = rs * (v[k][c] * gam[k][c] - m1 - xh[k][c] * m2);
+                for (int c = 0; c < 4; ++c) o[c] = ln_bwd_inner(v[k][c], gam[k][c], xh[k][c], m1, m2);
                 if (dadd) {
                     const float4 e = cur.e[k];
-                    o[0] += e.x; o[1] += e.y; o[2] += e.z; o[3] += e.w;
+                    o[0] = __builtin_fmaf(rs, o[0], e.x); o[1] = __builtin_fmaf(rs, o[1], e.y);
+                    o[2] = __builtin_fmaf(rs, o[2], e.z); o[3] = __builtin_fmaf(rs, o[3], e.w);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) o[c] *= rs;
                 }
                 *reinterpret_cast<float4*>(dx + base + c0) = make_float4(o[0], o[1], o[2], o[3]);
                 if (dx16) {
@@ -461,11 +487,7 @@ __global__ __launch_bounds__(256) void ln_bwd_pair_kernel(const float* __restric
                 for (int c = 0; c < 4; ++c) {
                     v[k][c] = av[c];
                     xh[k][c] = (bv[c] - cur.mu1) * cur.rs1;
-                    const float dxh = v[k][c] * gam1[k][c];
-                    m1 += dxh;
-                    m2 += dxh * xh[k][c];
-                    ag1[k][c] += v[k][c] * xh[k][c];
-                    ab1[k][c] += v[k][c];
+                    ln_bwd_terms(v[k][c], gam1[k][c], xh[k][c], m1, m2, ag1[k][c], ab1[k][c]);
                 }
             } else {
 #pragma unroll
@@ -482,13 +504,9 @@ __global__ __launch_bounds__(256) void ln_bwd_pair_kernel(const float* __restric
                 const float ev[4] = {e.x, e.y, e.z, e.w}, fv[4] = {f.x, f.y, f.z, f.w};
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
-                    v[k][c] = cur.rs1 * (v[k][c] * gam1[k][c] - m1 - xh[k][c] * m2) + ev[c];        // dy
+                    v[k][c] = __builtin_fmaf(cur.rs1, ln_bwd_inner(v[k][c], gam1[k][c], xh[k][c], m1, m2), ev[c]);        // dy
                     xh[k][c] = (fv[c] - cur.mu2) * cur.rs2;
-                    const float dxh = v[k][c] * gam2[k][c];
-                    n1 += dxh;
-                    n2 += dxh * xh[k][c];
-                    ag2[k][c] += v[k][c] * xh[k][c];
-                    ab2[k][c] += v[k][c];
+                    ln_bwd_terms(v[k][c], gam2[k][c], xh[k][c], n1, n2, ag2[k][c], ab2[k][c]);
                 }
             }
         }
@@ -500,7 +518,7 @@ __global__ __launch_bounds__(256) void ln_bwd_pair_kernel(const float* __restric
             if (c0 < d) {
                 float o[4], m[4];
 #pragma unroll
-                for (int c = 0; c < 4; ++c) o[c] = cur.rs2 * (v[k][c] * gam2[k][c] - n1 - xh[k][c] * n2);
+                for (int c = 0; c < 4; ++c) o[c] = cur.rs2 * ln_bwd_inner(v[k][c], gam2[k][c], xh[k][c], n1, n2);
                 *reinterpret_cast<float4*>(dx + base + c0) = make_float4(o[0], o[1], o[2], o[3]);
                 drop_mult4(xdrop, base + c0, m);
                 uint2 w;
