@@ -1535,6 +1535,10 @@ __global__ __launch_bounds__(NTH8, 1) void gemm_tn_bf16_v8_kernel(const FP p) {
         }
     };
     auto prologue = [&]() {
+        // an empty K-range (8 S ranges of `per` K-tiles reach past the reduction: 34 K-tiles in 32 ranges of 2 leave 15 of them empty) stages nothing: its
+        // K-tile 0 lies up to 8 S per K-tiles past the last row of A and B, and the loads were issued (and dropped) all the same - an illegal address
+        // where nothing is mapped behind A (tests/test_joint_rows_gpu.py, E2).  nk is uniform over the workgroup
+        if (nk <= 0) return;
         stage(0, 0, 0); stage(2, 0, 0); stage(3, 0, 0); stage(1, 0, 0);
         // K-tile 0 must have landed at the loop's first wait; tile 1's three half-tiles may fly (one K-tile only: that wait is a full drain)
         if (nk > 1) { TTMI_VM_GUARD("v8"); stage(0, 1, 1); stage(2, 1, 1); stage(3, 1, 1); }
@@ -1829,7 +1833,7 @@ __global__ __launch_bounds__(NTH8, 1) void gemm_tn_bf16_v9_kernel(const FP p) {
     int bm = 0, bn = 0, tn = 0;
     int it = cu;
     bool live = it < nitems;
-    if (live) { item(it, bm, bn, tn); sources(bm, bn, kbeg); stage(0, 0); if (nk > 1) { TTMI_VM_GUARD("v9"); stage(1, 1); } }
+    if (live) { item(it, bm, bn, tn); sources(bm, bn, kbeg); if (nk > 0) stage(0, 0); if (nk > 1) { TTMI_VM_GUARD("v9"); stage(1, 1); } }      // (nk == 0: an empty K-range past the reduction stages nothing, see TN v8's prologue)
     while (live) {
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -1897,7 +1901,7 @@ __global__ __launch_bounds__(NTH8, 1) void gemm_tn_bf16_v9_kernel(const FP p) {
         const int cbm = bm, cbn = bn, cunit = cs_unit;
         it += ncu;
         live = it < nitems;
-        if (live) { item(it, bm, bn, tn); sources(bm, bn, kbeg); stage(0, 0); if (nk > 1) { TTMI_VM_GUARD("v9"); stage(1, 1); } }
+        if (live) { item(it, bm, bn, tn); sources(bm, bn, kbeg); if (nk > 0) stage(0, 0); if (nk > 1) { TTMI_VM_GUARD("v9"); stage(1, 1); } }      // (nk == 0: an empty K-range past the reduction stages nothing, see TN v8's prologue)
 
         if (cnk > 0) {
             // atomics run at the memory side and want whole contiguous segments per wave-instruction: the accumulators (a lane holds 4
