@@ -232,6 +232,35 @@ int ttmi_ctc_loss_bwd(const float* logits, long ldv, const int* labels, const in
 int ttmi_ctc_greedy(const float* logits, long ld, const int* act_lens, int B, int T, int V, int blank,
                     int* tokens /* [B, T] */, int* count /* [B] */, void* stream);
 
+/* ---- monotonic RNN-T loss (Tripathi et al. 2019, "Monotonic RNN-T"; no reference counterpart) --------------------------------------------
+ * The forward-backward over the lattice the decoders of this library walk (ttmi_greedy_*, ttmi_beam_step[_ctx]): every frame makes exactly
+ * ONE decision, blank or one label, and the emitting frame is consumed - where the standard lattice above lets a label keep its frame.
+ * Arguments as for ttmi_rnnt_loss_fwd / _bwd: logits [B,T,U1,V] (dtype 0 = f32, 1 = bf16), row pitch ldv >= V; labels i32 [B,U1-1], clamped
+ * to [0, V-1]; act_lens, label_lens i32 [B], clamped as in the RNN-T loss (T_b to [1, T], U_b to [0, U1-1]); blank in [0, V); U1 <= 1024.
+ * With lp = log_softmax(z[b,t,u,:]), lpb(t,u) = lp[blank], lpl(t,u) = lp[y_{u+1}] for u < U_b:
+ *     alpha(0,0) = 0, alpha(0,u>0) = -inf
+ *     alpha(t+1,u) = logaddexp(alpha(t,u) + lpb(t,u), alpha(t,u-1) + lpl(t,u-1))                 0 <= t < T_b, 0 <= u <= U_b
+ *     ll = alpha(T_b, U_b),  costs[b] = -ll          (no terminal blank: after T_b decisions the path ends)
+ *     beta(T_b,U_b) = 0, beta(T_b,u<U_b) = -inf
+ *     beta(t,u) = logaddexp(lpb(t,u) + beta(t+1,u), lpl(t,u) + beta(t+1,u+1))
+ * ttmi_mono_loss_bwd, with g = scale * grad_out[b * grad_out_stride], for t < T_b, u <= U_b:
+ *     occ = exp(alpha(t,u) + beta(t,u) - ll)
+ *     e_b = exp(alpha(t,u) + lpb(t,u) + beta(t+1,u) - ll)
+ *     e_l = exp(alpha(t,u) + lpl(t,u) + beta(t+1,u+1) - ll)            (0 for u = U_b)
+ *     d z[k] = g * ( softmax_k * occ - [k == blank] e_b - [k == y_{u+1}] e_l )
+ * Every row sums to zero (occ = e_b + e_l).  A label equal to `blank` is not rejected: both patches then land on one column.  Rows outside
+ * [0,T_b) x [0,U_b] are exact zeros, columns [V, ldg) are zeros; grad (the logits' dtype, pitch ldg) may alias logits when ldg == ldv.
+ * An utterance with U_b > T_b has no path: costs[b] = +inf and all-zero gradient rows, never NaN (the rule of the CTC entries).
+ * Alpha and beta are carried in fp64.  workspace: ttmi_mono_workspace_bytes(B, T, U1) bytes, 8-byte aligned, a layout of its own (NOT the
+ * one ttmi_rnnt_align / _emit_stats read); the forward fills it, the backward reads it.  No allocation, host synchronisation, memset node
+ * or floating-point atomic: both calls may be captured in a HIP graph, and two runs give the same bits. */
+size_t ttmi_mono_workspace_bytes(int B, int T, int U1);
+int ttmi_mono_loss_fwd(const void* logits, int dtype, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                       int B, int T, int U1, int V, int blank, void* workspace, float* costs, void* stream);
+int ttmi_mono_loss_bwd(const void* logits, int dtype, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                       int B, int T, int U1, int V, int blank, const void* workspace, const float* grad_out,
+                       int grad_out_stride, float scale, void* grad, long ldg, void* stream);
+
 /* ---- grouped weight gradients (data-parallel hot path): the four weight-gradient GEMMs of an encoder layer are a quarter
  * of the chip each step; deferred and launched four layers at a time they are 256 tiles, one per CU over the whole reduction - no split along
  * K, no atomics, bit-identical from run to run and across ranks.  ttmi_attn_bwd_defer / ttmi_ffn_bwd_defer are ttmi_attn_bwd / ttmi_ffn_bwd

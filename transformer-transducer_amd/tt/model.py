@@ -122,14 +122,19 @@ class _JointLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, enc, dec, wf, bf, wp, bp, labels, act_lens, label_lens, prec, chunk, reduction, exp_state, grad_mode=True, blank=0,
-                fastemit_lambda=0.0, weights=None):
+                fastemit_lambda=0.0, weights=None, topology="rnnt"):
         """exp_state: None (plain fused form) or the JointNet's _ExpShift for this device (exp-domain form); fastemit_lambda: the FastEmit
         weight of the loss gradient (warprnnt_pytorch.RNNTLoss), in all three chunk forms; weights: None or a constant f32 [B] on the device,
         one factor per utterance: the result is sum_b w_b cost_b (times 1 / B for 'mean') and every chunk's loss-gradient call reads its slice
         of w as its upstream gradient (grad_out_stride = 1), so the gradients formed here are those of the weighted sum.  A chunk whose
         weights are all zero is NOT skipped: its costs are part of the result either way, and knowing that its weights are zero would take a
-        host read of a device tensor - its gradient kernels run and add exact zeros"""
+        host read of a device tensor - its gradient kernels run and add exact zeros; topology: 'rnnt', or 'monotonic' for the decoders'
+        one-decision-per-frame lattice (ttmi_mono_loss_fwd / _bwd): that one has the plain chunk form only - joint_fwd, mono_loss_fwd,
+        mono_loss_bwd in place, joint_bwd - no exp-domain form, no pre-split gradient planes and no shift seeding"""
         fe = ops.check_fastemit(fastemit_lambda)
+        mono = ops.check_topology(topology, fe) == "monotonic"
+        if mono and exp_state is not None:
+            raise ValueError("topology='monotonic' has no exp-domain form")
         enc, dec = enc.contiguous(), dec.contiguous()
         params = (wf, bf, wp, bp)
         wf_, bf_, wp_, bp_ = (t.detach() for t in params)
@@ -154,8 +159,17 @@ class _JointLossFn(torch.autograd.Function):
             st.poll()
         for c0 in range(0, B, chunk):
             c1 = min(B, c0 + chunk)
-            ws = ops.rnnt_workspace(c1 - c0, T, U1, enc.device)
             lab, al, ll = labels[c0:c1], act_lens[c0:c1], label_lens[c0:c1]
+            if mono:
+                ws = ops.mono_workspace(c1 - c0, T, U1, enc.device)
+                logits, saved = ops.joint_fwd(enc[c0:c1], dec[c0:c1], wf_, bf_, wp_, bp_, prec)
+                costs[c0:c1] = ops.mono_loss_fwd(logits, lab, al, ll, blank, ws)
+                if need:
+                    grad = ops.mono_loss_bwd(logits, lab, al, ll, blank, ws, *upstream(c0, c1), scale, inplace=True)
+                    ops.joint_bwd(grad, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
+                del logits, saved
+                continue
+            ws = ops.rnnt_workspace(c1 - c0, T, U1, enc.device)
             exp_ok = st is not None and ops.joint_exp_supported(c1 - c0, T, U1, J, V, prec, fwd_only=not need)
             if st is not None and not exp_ok:
                 _warn_no_exp(c1 - c0, T, U1, J, V)
@@ -215,7 +229,7 @@ class _JointLossFn(torch.autograd.Function):
                     cb()
             else:
                 rets.append(gp * gout)
-        return (denc * gout, ddec * gout, *rets, None, None, None, None, None, None, None, None, None, None, None)
+        return (denc * gout, ddec * gout, *rets, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
 class _CTCHeadLossFn(torch.autograd.Function):
@@ -419,7 +433,7 @@ class DeferredLogits(torch.Tensor):
                 self._real = self._produce()
         return self._real
 
-    def rnnt_loss(self, labels, act_lens, label_lens, blank=0, reduction="mean", *, fastemit_lambda=0.0):
+    def rnnt_loss(self, labels, act_lens, label_lens, blank=0, reduction="mean", *, fastemit_lambda=0.0, topology="rnnt"):
         """the loss of train.py:53 on this handle's logits without forming them (called by warprnnt_pytorch.rnnt_loss; arguments already
         certified there).  None when this case has to go through the real logits (per-utterance costs that need gradients)."""
         if self._real is not None:
@@ -430,6 +444,11 @@ class DeferredLogits(torch.Tensor):
         j = self._joint
         B, T, U1 = self.shape[0], self.shape[1], self.shape[2]
         ops.weights_fresh()
+        if topology == "monotonic":         # the plain (non-exp) chunk form, at the memory form's chunk size
+            chunk = j.default_loss_chunk(B, T, U1, False, self._prec)
+            return _JointLossFn.apply(self._enc, self._dec, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
+                                      j.project_layer.bias, labels, act_lens, label_lens, self._prec, int(chunk), reduction, None, grad,
+                                      int(blank), fastemit_lambda, None, topology)
         exp = self._prec == 1 and os.environ.get("TTMI_DEFERRED_EXP", "1") != "0"
         chunk = j.default_loss_chunk(B, T, U1, exp, self._prec)
         if exp and not ops.joint_exp_supported(chunk, T, U1, j.forward_layer.out_features, j.project_layer.out_features, self._prec,
@@ -657,7 +676,7 @@ class Transducer(nn.Module):
         return self.joint(enc_state, dec_state)
 
     def loss(self, inputs, inputs_length, targets, targets_length, reduction="mean", chunk=None, check_lengths=True, exp_domain=False, *,
-             fastemit_lambda=0.0, ctc_weight=None, utterance_weights=None):
+             fastemit_lambda=0.0, ctc_weight=None, utterance_weights=None, topology="rnnt"):
         """Opt-in fused form of train.py:51-53 (`logits = model(inputs, targets); loss = criterion(logits, targets.int(),
         inputs_length.int(), targets_length.int())`) that never materialises the logits (API precedent: tt_espnet/model.py:35-81 returns
         the loss from forward).  Same numbers as the two-call form: the same kernels run, one chunk of `chunk` utterances at a time
@@ -678,9 +697,16 @@ class Transducer(nn.Module):
         utterance_weights (None: today's code path and bits): an f32 / f64 tensor [B] on the device, one constant factor per utterance (no
         gradient flows into it; zero and negative entries are allowed).  The transducer term becomes sum_b w_b cost_b for 'sum' and that
         over B for 'mean'; its gradient is formed in the forward pass as always, each chunk's loss-gradient kernel reading its slice of w
-        (all three chunk forms).  ValueError with reduction='none'.  The CTC term, when asked for, is not weighted."""
-        from warprnnt_pytorch import check_lengths as certify
+        (all three chunk forms).  ValueError with reduction='none'.  The CTC term, when asked for, is not weighted.
+
+        topology ('rnnt': today's code path and bits): 'monotonic' trains the one-decision-per-frame lattice the decoders of this class walk
+        (warprnnt_pytorch.RNNTLoss has the same option) in the plain chunk form; ValueError together with exp_domain=True or
+        fastemit_lambda > 0, and, under check_lengths, for an utterance with more labels than frames."""
+        from warprnnt_pytorch import check_lengths as certify, check_monotonic_lengths as monotonic_lengths
         fastemit_lambda = ops.check_fastemit(fastemit_lambda)
+        mono = ops.check_topology(topology, fastemit_lambda) == "monotonic"
+        if mono and exp_domain:
+            raise ValueError("topology='monotonic' has no exp-domain form: leave exp_domain off")
         ctc_weight = self._ctc_weight(ctc_weight)
         if utterance_weights is not None:
             utterance_weights = self._utterance_weights(utterance_weights, inputs.shape[0], reduction)
@@ -688,6 +714,8 @@ class Transducer(nn.Module):
         B, T, U1 = enc_state.shape[0], enc_state.shape[1], dec_state.shape[1]
         labels, al, ll = (t.to(device=enc_state.device, dtype=torch.int32).contiguous() for t in (targets, inputs_length, targets_length))
         certify(labels, al, ll, B, T, U1, check_lengths)
+        if mono and check_lengths:
+            monotonic_lengths(al, ll)                # ValueError for an utterance with more labels than frames
         ops.weights_fresh()
         prec = default_precision()
         if chunk is None:
@@ -696,7 +724,7 @@ class Transducer(nn.Module):
         rnnt = _JointLossFn.apply(enc_state, dec_state, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
                                   j.project_layer.bias, labels, al, ll, prec, int(chunk), reduction,
                                   j.exp_shift_state(enc_state.device) if exp_domain and prec == 1 else None, torch.is_grad_enabled(), 0,
-                                  fastemit_lambda, utterance_weights)
+                                  fastemit_lambda, utterance_weights, topology)
         if ctc_weight > 0.0:
             return rnnt + ctc_weight * self._ctc_from_states(enc_state, labels, al, ll, reduction)
         return rnnt
@@ -735,7 +763,7 @@ class Transducer(nn.Module):
                                     reduction, torch.is_grad_enabled(), 0)
 
     def mwer_loss(self, inputs, inputs_length, targets, targets_length, *, beam_width=4, nbest=None, rnnt_weight=0.0, hypotheses=None,
-                  chunk=None, fastemit_lambda=0.0, details=False):
+                  chunk=None, fastemit_lambda=0.0, details=False, topology="rnnt"):
         """Minimum word error rate training on the N-best list (Prabhavalkar et al. 2018; Guo et al. 2020 for RNN-T), on tokens: utterance b
         has the distinct hypotheses y_1 .. y_n; c_i = the RNN-T lattice cost of (x_b, y_i), as loss(reduction='none') gives it;
         P_i = softmax_i(-c_i) in float64; W_i = the edit distance of y_i to the transcript; E_b = sum_i P_i W_i.  Returns, as an f64 [1],
@@ -754,10 +782,15 @@ class Transducer(nn.Module):
         pass 1 under no_grad gives c, pass 2 with utterance_weights = w forms the gradient - the [rows, T, U+1, V] logits never exist, one
         chunk of `chunk` ROWS at a time (default: default_loss_chunk of the row count).  fastemit_lambda acts on pass 2's gradient.
 
+        topology ('rnnt' / 'monotonic', as in `loss`) is the lattice of both passes: with 'monotonic' the hypothesis costs c_i are taken on the
+        lattice whose path sums ranked the N-best (the beam search's merged scores).  A hypothesis of the beam search never has more tokens
+        than its utterance has frames; hypotheses passed in must not either (such a row has no path on this lattice: its cost is +inf).
+
         details=True: -> (loss, MWERDetails(hypotheses, errors i32 [rows], posteriors f64 [rows], costs f32 [rows], expected_errors f64 [B]));
         the per-row fields cover the whole row table: transcript rows carry errors 0 and posterior 0."""
         from ttmi import metrics
         fastemit_lambda = ops.check_fastemit(fastemit_lambda)
+        ops.check_topology(topology, fastemit_lambda)
         rnnt_weight = float(rnnt_weight)
         if not rnnt_weight >= 0.0:
             raise ValueError("mwer_loss: rnnt_weight must be >= 0, got %r" % (rnnt_weight,))
@@ -821,7 +854,7 @@ class Transducer(nn.Module):
 
         def fused(reduction, grad, fe, w):
             return _JointLossFn.apply(enc_rows, dec_rows, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
-                                      j.project_layer.bias, labels32, al32, ll32, prec, int(chunk), reduction, None, grad, 0, fe, w)
+                                      j.project_layer.bias, labels32, al32, ll32, prec, int(chunk), reduction, None, grad, 0, fe, w, topology)
         with torch.no_grad():
             costs = fused("none", False, 0.0, None)                                               # pass 1
         wt = metrics.mwer_weights(costs[:n_hyp], errors[:n_hyp], row_utt, B, max_per_utt=n_max)

@@ -164,6 +164,9 @@ def main(argv=None):
         dist.broadcast(se, 0)
         start_epoch = int(se)
     criterion = RNNTLoss(fastemit_lambda=config.training.get('fastemit_lambda', 0.0))     # FastEmit: an optional key of this driver
+    topology = config.training.get('loss_topology', 'rnnt')     # the loss lattice, another optional key: 'monotonic' = the decoders' one-decision-per-frame lattice
+    if topology != 'rnnt':
+        criterion = RNNTLoss(fastemit_lambda=criterion.fastemit_lambda, topology=topology)
     if ctc_weight > 0.0:
         criterion = CTCAugmentedCriterion(criterion, model, ctc_weight)
     for epoch in range(start_epoch, config.training.epochs):

@@ -130,6 +130,63 @@ def rnnt_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_o
     return grad
 
 
+# ----------------------------------------------------------------------------- monotonic RNN-T loss (the decoders' one-symbol-per-frame lattice)
+def mono_workspace(B, T, U1, device):
+    f = lib().ttmi_mono_workspace_bytes
+    f.restype = ctypes.c_size_t
+    n = f(c_int(B), c_int(T), c_int(U1))
+    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+
+
+def mono_loss_fwd(logits, labels, act_lens, label_lens, blank, workspace):
+    """logits: f32/bf16 [B,T,U1,V], dense or row-padded view -> costs f32 [B] on the monotonic lattice (include/ttmi.h)"""
+    _need_cuda(logits, labels, act_lens, label_lens, workspace)
+    B, T, U1, V = logits.shape
+    ld = row_pitch(logits)
+    assert ld is not None
+    costs = torch.empty(B, dtype=torch.float32, device=logits.device)
+    check(lib().ttmi_mono_loss_fwd(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
+                                   c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(costs), _stream()),
+          "ttmi_mono_loss_fwd")
+    return costs
+
+
+def mono_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, inplace=False):
+    """inplace: the gradient overwrites the logits (same dtype and pitch), as in rnnt_loss_bwd"""
+    _need_cuda(logits, labels, act_lens, label_lens, workspace, grad_out)
+    B, T, U1, V = logits.shape
+    ld = row_pitch(logits)
+    assert ld is not None
+    if inplace:
+        buf = grad = logits
+        ldg = ld
+    elif ld == V:
+        buf = grad = torch.empty_like(logits)
+        ldg = V
+    else:
+        buf = torch.empty(B, T, U1, ld, dtype=logits.dtype, device=logits.device)
+        grad, ldg = buf[..., :V], ld
+    check(lib().ttmi_mono_loss_bwd(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
+                                   c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(grad_out),
+                                   c_int(grad_out_stride), c_float(scale), _p(grad), c_long(ldg), _stream()),
+          "ttmi_mono_loss_bwd")
+    if ldg != V:
+        grad._ttmi_zero_pad = ldg
+    return grad
+
+
+TOPOLOGIES = ("rnnt", "monotonic")
+
+
+def check_topology(topology, fastemit_lambda=0.0):
+    """-> topology; ValueError unless it names a lattice the loss kernels walk, or for FastEmit on the monotonic one (not built)"""
+    if topology not in TOPOLOGIES:
+        raise ValueError("topology must be 'rnnt' or 'monotonic', got %r" % (topology,))
+    if topology == "monotonic" and fastemit_lambda > 0.0:
+        raise ValueError("topology='monotonic' does not take fastemit_lambda > 0 (FastEmit is defined on the standard lattice here)")
+    return topology
+
+
 # ----------------------------------------------------------------------------- CTC loss / greedy decode (auxiliary head on the audio encoder)
 def ctc_workspace(B, T, U, device):
     f = lib().ttmi_ctc_workspace_bytes

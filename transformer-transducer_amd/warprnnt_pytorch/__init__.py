@@ -14,6 +14,11 @@ regularisation (Yu et al., ICASSP 2021) as the transducer-loss libraries
 expose it: the gradient favours emitting a label over emitting blank, the
 returned cost stays -log P(y|x).  Formula: include/ttmi.h.
 
+`topology` (keyword-only, default "rnnt") selects the lattice: "rnnt" is the
+standard one (a label keeps its frame; warp-transducer's), "monotonic" the
+one-symbol-per-frame lattice of this package's decoders (Tripathi et al. 2019;
+csrc/mono.hip, recursion in include/ttmi.h).  FastEmit is not built on it.
+
 `rnnt_align` (no counterpart in warp-transducer, which returns costs only) is
 forced alignment on the same arguments: the best path through the lattice
 (frame of every label's emission), its log-probability, the cost, and on
@@ -27,7 +32,7 @@ import torch
 
 from ttmi import ops
 
-__all__ = ["RNNTLoss", "rnnt_loss", "rnnt_align", "AlignResult", "check_lengths"]
+__all__ = ["RNNTLoss", "rnnt_loss", "rnnt_align", "AlignResult", "check_lengths", "check_monotonic_lengths"]
 
 
 _max_cache = {}     # id(tensor) -> (weakref, tensor._version, max): the length check costs a device-to-host sync; a lengths tensor that
@@ -43,6 +48,22 @@ def _cached_max(t):
         _max_cache.clear()
     _max_cache[id(t)] = (weakref.ref(t), t._version, v)
     return v
+
+
+def check_monotonic_lengths(act_lens, label_lens):
+    """the monotonic lattice has no path for an utterance with more labels than frames.  One device-to-host read, under check_lengths only,
+    and like _cached_max not repeated for the SAME two tensor objects at the same version counters"""
+    key = (id(act_lens), id(label_lens))
+    ent = _max_cache.get(key)
+    if ent is not None and ent[0]() is act_lens and ent[1]() is label_lens and ent[2] == (act_lens._version, label_lens._version):
+        bad = ent[3]
+    else:
+        bad = bool((label_lens > act_lens).any())
+        if len(_max_cache) > 64:
+            _max_cache.clear()
+        _max_cache[key] = (weakref.ref(act_lens), weakref.ref(label_lens), (act_lens._version, label_lens._version), bad)
+    if bad:
+        raise ValueError("topology='monotonic': an utterance has more labels than frames (label_lengths > lengths)")
 
 
 def _certify(acts, labels, act_lens, label_lens, check_lengths):
@@ -114,23 +135,60 @@ class _RNNTLossFn(torch.autograd.Function):
         return grad, None, None, None, None, None, None
 
 
-def rnnt_loss(acts, labels, act_lens, label_lens, blank=0, reduction="mean", check_lengths=None, *, fastemit_lambda=0.0):
+def rnnt_loss(acts, labels, act_lens, label_lens, blank=0, reduction="mean", check_lengths=None, *, fastemit_lambda=0.0, topology="rnnt"):
     fastemit_lambda = ops.check_fastemit(fastemit_lambda)
+    mono = ops.check_topology(topology, fastemit_lambda) == "monotonic"
     if check_lengths is None:
         check_lengths = os.environ.get("TTMI_CHECK_LENGTHS", "1") != "0"
     if not acts.is_cuda:
         raise ValueError("RNNTLoss: acts must live on the GPU (the MI355X build has no CPU path)")
     labels, act_lens, label_lens = (t.to(acts.device) for t in (labels, act_lens, label_lens))
     _certify(acts, labels, act_lens, label_lens, check_lengths)      # (shape / dtype queries only: a DeferredLogits handle stays a handle)
+    if mono and check_lengths:
+        check_monotonic_lengths(act_lens, label_lens)
     fused = getattr(acts, "rnnt_loss", None)
-    if fused is not None:
+    if fused is not None and mono:
+        out = fused(labels, act_lens, label_lens, int(blank), reduction, topology="monotonic")
+        if out is not None:
+            return out
+        acts = acts.materialize()
+    elif fused is not None:
         # `acts` is the handle Transducer.forward returns in the bf16 pipeline (tt.model.DeferredLogits): joint + loss run as one fused op on
         # the encoder states it carries and the logits are never formed - train.py:51-53 as written, on the path of Transducer.loss
         out = fused(labels, act_lens, label_lens, int(blank), reduction, fastemit_lambda=fastemit_lambda)
         if out is not None:
             return out
         acts = acts.materialize()           # (per-utterance costs with gradients, or a handle that was already used as a tensor)
+    if mono:
+        return _MonoLossFn.apply(acts, labels, act_lens, label_lens, int(blank), reduction)
     return _RNNTLossFn.apply(acts, labels, act_lens, label_lens, int(blank), reduction, fastemit_lambda)
+
+
+class _MonoLossFn(torch.autograd.Function):
+    """_RNNTLossFn on the monotonic lattice (ttmi_mono_loss_fwd / _bwd)"""
+
+    @staticmethod
+    def forward(ctx, acts, labels, act_lens, label_lens, blank, reduction):
+        B, T, U1, _ = acts.shape
+        acts_c = acts if ops.row_pitch(acts) is not None else acts.contiguous()     # row-padded views are consumed in place
+        ws = ops.mono_workspace(B, T, U1, acts.device)
+        costs = ops.mono_loss_fwd(acts_c, labels, act_lens, label_lens, blank, ws)
+        ctx.save_for_backward(acts_c, labels, act_lens, label_lens, ws)
+        ctx.blank, ctx.reduction = blank, reduction
+        if reduction == "none":
+            return costs
+        out = costs.sum().reshape(1)
+        return out / B if reduction == "mean" else out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        acts, labels, act_lens, label_lens, ws = ctx.saved_tensors
+        B = acts.shape[0]
+        go = grad_out.contiguous().float()
+        per_utt = ctx.reduction == "none"
+        scale = 1.0 / B if ctx.reduction == "mean" else 1.0
+        grad = ops.mono_loss_bwd(acts, labels, act_lens, label_lens, ctx.blank, ws, go, 1 if per_utt else 0, scale)
+        return grad, None, None, None, None, None
 
 
 class AlignResult(NamedTuple):
@@ -175,19 +233,24 @@ def rnnt_align(acts, labels, act_lens, label_lens, blank=0, check_lengths=None, 
 
 
 class RNNTLoss(torch.nn.Module):
-    """RNNTLoss(blank=0, reduction='mean', *, fastemit_lambda=0.0)(acts, labels, act_lens, label_lens)
+    """RNNTLoss(blank=0, reduction='mean', *, fastemit_lambda=0.0, topology='rnnt')(acts, labels, act_lens, label_lens)
+
+    topology: 'rnnt' (the standard lattice, the default, bit for bit what it was) or 'monotonic' (one decision per frame, the lattice of
+    this package's decoders; with the length check on, an utterance with more labels than frames is a ValueError, with it off such an
+    utterance costs +inf and has a zero gradient).  'monotonic' with fastemit_lambda > 0 is a ValueError.
 
     fastemit_lambda: FastEmit regularisation weight (finite, >= 0; 0 is the plain loss, bit for bit).  It changes the gradient only.
     It reaches the kernels as a by-value argument, so a captured step (ttmi.train.GraphedStep) replays the value it was captured with:
     changing it means recapturing."""
 
-    def __init__(self, blank=0, reduction="mean", check_lengths=None, *, fastemit_lambda=0.0):
+    def __init__(self, blank=0, reduction="mean", check_lengths=None, *, fastemit_lambda=0.0, topology="rnnt"):
         super().__init__()
         if reduction not in ("mean", "sum", "none"):
             raise ValueError("reduction must be 'mean', 'sum' or 'none'")
         self.blank, self.reduction, self.check_lengths = blank, reduction, check_lengths
         self.fastemit_lambda = ops.check_fastemit(fastemit_lambda)
+        self.topology = ops.check_topology(topology, self.fastemit_lambda)
 
     def forward(self, acts, labels, act_lens, label_lens):
         return rnnt_loss(acts, labels, act_lens, label_lens, self.blank, self.reduction, self.check_lengths,
-                         fastemit_lambda=self.fastemit_lambda)
+                         fastemit_lambda=self.fastemit_lambda, topology=self.topology)
