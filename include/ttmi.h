@@ -261,6 +261,38 @@ int ttmi_mono_loss_bwd(const void* logits, int dtype, long ldv, const int* label
                        int B, int T, int U1, int V, int blank, const void* workspace, const float* grad_out,
                        int grad_out_stride, float scale, void* grad, long ldg, void* stream);
 
+/* ---- forced alignment and emission-time statistics on the monotonic lattice (no reference counterpart) ---------------------------------
+ * The twins of ttmi_rnnt_align / _emit_stats on the lattice above.  Both READ the workspace a finished ttmi_mono_loss_fwd left on the same
+ * (B, T, U1) - lpb, lpl, alpha, beta, ll - and write nothing into it: a ttmi_mono_loss_bwd issued after them gives the same bits as one
+ * issued straight after the forward.  Lengths are clamped as in the loss (T_b to [1, T], U_b to [0, U1-1]); U1 <= 1024.
+ * ttmi_mono_align: the best path, frontier in fp64 like alpha / beta.
+ *     v(0,0) = 0, v(0,u>0) = -inf
+ *     v(t+1,u) = max(v(t,u) + lpb(t,u), v(t,u-1) + lpl(t,u-1))                                     0 <= t < T_b, 0 <= u <= U_b
+ *     score[b] = (float) v(T_b, U_b)                  (no terminal blank), the log-probability of that path
+ * TIE RULE: the label move is taken only when it is strictly greater; a tie goes to blank.  The backtrace runs from (T_b, U_b) backwards in
+ * time, so on all-equal logits it yields frames = 0, 1, ..., U_b-1.  frames i32 [B, U1-1]: frames[b][u] = the frame whose one decision is
+ * label u+1 (the path's move (t, u) -> (t+1, u+1)), STRICTLY increasing in u (ttmi_rnnt_align's is only non-decreasing), -1 for u >= U_b.
+ * This is the lattice of ttmi_greedy_advance_lp's and ttmi_beam_step's scores: score[b] is an upper bound of the score of any decoder path
+ * that spells the same labels.  An utterance with U_b > T_b has no path: score[b] = -inf and every frames entry -1, never NaN; its
+ * neighbours are unaffected.  Whatever the workspace holds, NaN included, the backtrace follows no index outside its arrays and writes
+ * nothing outside the utterance's frames row: with u labels left at frame t it keeps u <= t + 1 (the move is a label whatever the stored
+ * bit says once u = t + 1, a blank once u = 0).  One decision bit per cell: kept in LDS when an utterance's T * ceil(U1 / 64) 8-byte words
+ * fit (128 KB), otherwise in align_workspace (ttmi_mono_align_workspace_bytes(B, T, U1) bytes, 8-byte aligned, always required, contents
+ * undefined afterwards).  ttmi_set_option(23, bits) is honoured as by ttmi_rnnt_align - measurements / tests only: 1 = decision words in
+ * align_workspace whatever the shape, 2 = no backtrace.
+ * ttmi_mono_emit_stats: e(t,u) = exp(alpha(t,u) + lpl(t,u) + beta(t+1,u+1) - ll) for u < U_b, t < T_b is the posterior probability that
+ * label u+1 is frame t's decision; mass f32 [B, U1-1] = sum_t e(t,u) (1 for a healthy lattice: every path emits every label once), expected
+ * f32 [B, U1-1] = sum_t t e(t,u), the expected emission frame.  Entries u >= U_b: mass 0, expected -1; an utterance without a path: mass 0
+ * and expected -1 in every entry.  The sums are fp64 in a fixed order, no floating-point atomics: two runs give the same bits.
+ * Neither call allocates, synchronises with the host or issues a memset node; both may be captured in a HIP graph.  rc < 0 with a
+ * ttmi_last_error text, before any launch, on a null pointer or a shape outside the limits. */
+size_t ttmi_mono_align_workspace_bytes(int B, int T, int U1);
+int ttmi_mono_align(const void* workspace /* filled by ttmi_mono_loss_fwd on the same (B,T,U1) */,
+                    const int* act_lens, const int* label_lens, int B, int T, int U1,
+                    void* align_workspace, int* frames, float* score, void* stream);
+int ttmi_mono_emit_stats(const void* workspace, const int* act_lens, const int* label_lens, int B, int T, int U1,
+                         float* expected, float* mass, void* stream);
+
 /* ---- grouped weight gradients (data-parallel hot path): the four weight-gradient GEMMs of an encoder layer are a quarter
  * of the chip each step; deferred and launched four layers at a time they are 256 tiles, one per CU over the whole reduction - no split along
  * K, no atomics, bit-identical from run to run and across ranks.  ttmi_attn_bwd_defer / ttmi_ffn_bwd_defer are ttmi_attn_bwd / ttmi_ffn_bwd
@@ -345,7 +377,8 @@ int ttmi_greedy_advance(unsigned long long* key, int B, int n, int n_hist, long*
  * score[b] is the log-probability of the decisions the greedy decoder took: each of the utterance's T_b frames contributes one term, blank's
  * log-probability against the label state current at that frame on a frame that does not emit, the symbol's on a frame that does (the emitting
  * frame is consumed: at most one symbol per frame).  That is the path of this decoder, NOT a path of the RNN-T lattice (the lattice follows a
- * label with a blank on the same frame): it is not comparable with ttmi_rnnt_align's score.
+ * label with a blank on the same frame): it is not comparable with ttmi_rnnt_align's score.  It IS a path of the monotonic lattice: the
+ * score ttmi_mono_align gives for the same labels is its upper bound, and equal to it when the two paths emit at the same frames.
  * Neither call allocates, synchronises with the host or issues a memset node; both may be captured in a HIP graph. */
 int ttmi_greedy_scan_batch_lp(const void* logits, int dtype, long ld, int B, int n, int V, int blank, const int* t, const int* T_len,
                               const int* need, unsigned long long* key, float* lp, void* stream);
@@ -565,7 +598,7 @@ int ttmi_stream_reserve_cus(void* stream, int n);
  * workgroups end with one atomically added piece per workgroup instead of a second round; without a reservation the launches stay free of atomics either way);
  * 21: 0 = the joint's sums over frames (dPD) by f32 atomics as in rounds 1 - 5 (default 1: partial rows + an ordered second pass - the same bits in every run, same time);
  * 22: 0 = bf16x3 weight gradients as three accumulating launches (round 5) instead of one launch over the plane pairs + a fold;
- * 23: ttmi_rnnt_align bits: 1 = decision words in the caller's workspace whatever the shape, 2 = forward walk only, no backtrace (frames of real labels are not written) */
+ * 23: ttmi_rnnt_align / ttmi_mono_align bits: 1 = decision words in the caller's workspace whatever the shape, 2 = forward walk only, no backtrace (frames of real labels are not written) */
 int ttmi_set_option(int key, int value);
 int ttmi_dropout_apply(const float* in, long n, float p, unsigned seed, float* out, void* stream);
 int ttmi_probe_arm(int slot);

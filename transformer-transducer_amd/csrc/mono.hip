@@ -10,6 +10,9 @@
 //                          u-1 / u+1 neighbour arrives by a one-lane DPP wave rotate, and the cell that crosses a slot seam is the rotate's
 //                          wrapped lane of the neighbouring slot (a select, no LDS).  Emission rows are prefetched PF frames ahead.
 //   mono_grad_kernel       HBM-bound: one wave per row reads the logits once and writes the gradient once (in place allowed).
+//   mono_viterbi_kernel    forced alignment: the alpha walk with max in place of log-add-exp, one ballot word of decisions per frame and slot,
+//                          and the backtrace, in one launch (one wave per utterance).
+//   mono_emit_stats_kernel expected emission frame of every label from alpha / beta, lanes across the labels of a frame row.
 #include "common.h"
 #include "lattice.h"
 
@@ -282,9 +285,231 @@ __global__ __launch_bounds__(MONO_WAVES * 64) void mono_grad_kernel(
     for (int i = V + lane; i < ldg; i += 64) stf<TL>(g + i, 0.f);
 }
 
+// ------------------------------------------------------------------ forced alignment: best path through the monotonic lattice
+// v(0,0) = 0, v(t+1,u) = max(v(t,u) + lpb(t,u), v(t,u-1) + lpl(t,u-1)); the label move is taken only when it is STRICTLY greater (a tie goes
+// to blank).  It is the alpha half of mono_alphabeta_kernel with max in place of lae, in the same shape: one wave per utterance, lane l / slot
+// r owns label u = 64 r + l, the frontier in fp64 registers, the label term formed by its owner and rotated one lane, the slot seam a select
+// between two rotated registers, emission rows prefetched PF frames ahead (unconditional loads of a clamped index; what they bring from
+// outside the ragged lattice is dropped by selects, never by arithmetic).
+// The decision of a cell is one bit (1 = cell (t+1, u) was reached by the label move of frame t); per frame and slot that is one __ballot word,
+// stored by lane 0 at dec[t * W + r] - in LDS when the utterance's words fit, else in the caller's workspace.  The backtrace follows in the same
+// kernel: every move steps one frame down, so the path crosses frames T_b - 1 ... 0 in order, one decision each; the wave fetches the words of
+// 64 frames at a time (lane j: frame t - j, slot u / 64) and walks them by lane reads with t and u in scalar registers - a new fetch only after
+// 64 steps or when u leaves the slot.  The walk keeps u <= t + 1: with u = t + 1 labels left the move is a label whatever the bit says, with
+// u = 0 it is a blank, so it emits exactly U_b labels at strictly decreasing frames and ends at (0, 0) whatever the data (NaN included).
+typedef unsigned long long dec_t;
+
+template <int R, int PF, bool LDS_DEC>
+__global__ __launch_bounds__(64) void mono_viterbi_kernel(const float* __restrict__ lpb_g, const float* __restrict__ lpl_g,
+                                                          const int* __restrict__ act_lens, const int* __restrict__ label_lens, int T, int U1,
+                                                          int W, dec_t* __restrict__ dec_ws, int* __restrict__ frames,
+                                                          float* __restrict__ score, int backtrace) {
+    extern __shared__ __attribute__((aligned(16))) char mono_vit_smem[];
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U1 - 1);
+    const float* lpb = lpb_g + (long)b * T * U1;
+    const float* lpl = lpl_g + (long)b * T * U1;
+    dec_t* dec_l = reinterpret_cast<dec_t*>(mono_vit_smem);                 // [T_b][W] (LDS_DEC)
+    dec_t* dec_g = dec_ws + (long)b * T * W;                                // [T][W] per utterance (otherwise)
+    int* fr = frames + (long)b * (U1 - 1);
+    const bool no_path = Ub > Tb;                                           // wave-uniform: more labels than frames
+    for (int u = (no_path ? 0 : Ub) + lane; u < U1 - 1; u += 64) fr[u] = -1;      // labels the utterance does not have
+    if (no_path) {
+        if (lane == 0) score[b] = -INFINITY;
+        return;
+    }
+    bool vb[R], vl[R];                     // this slot's cell exists / has a label move
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int u = r * 64 + lane;
+        vb[r] = u <= Ub;
+        vl[r] = u < Ub;
+    }
+    MonoRows<R, PF> cur, nxt;
+    acc_t a[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) a[r] = (r == 0 && lane == 0) ? 0.0 : (acc_t)NEG;
+    mono_load_rows<R, PF>(cur, lpb, lpl, 0, 1, Tb, U1, lane);
+    for (int base = 0; base < Tb; base += PF) {
+        mono_load_rows<R, PF>(nxt, lpb, lpl, base + PF, 1, Tb, U1, lane);
+#pragma unroll
+        for (int s = 0; s < PF; ++s) {
+            const int t = base + s;
+            if (t < Tb) {                  // wave-uniform
+                acc_t x[R];
+#pragma unroll
+                for (int r = 0; r < R; ++r) x[r] = rot_r1(vl[r] ? a[r] + (acc_t)cur.pl[s][r] : (acc_t)NEG);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    // lane 0 of slot r: the wrapped lane 63 of slot r-1 (label 64 r - 1); nothing left of label 0
+                    const acc_t left = (lane == 0) ? (r > 0 ? x[r > 0 ? r - 1 : 0] : (acc_t)NEG) : x[r];
+                    const acc_t tt = a[r] + (acc_t)cur.pb[s][r];
+                    const bool lab = vb[r] && (r > 0 || lane > 0) && (left > tt);      // strictly greater: a tie goes to blank
+                    a[r] = vb[r] ? (lab ? left : tt) : (acc_t)NEG;
+                    const dec_t w = __ballot(lab);
+                    if (r < W && lane == 0) {
+                        if constexpr (LDS_DEC) dec_l[t * W + r] = w;
+                        else dec_g[(long)t * W + r] = w;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < PF; ++s)
+#pragma unroll
+            for (int r = 0; r < R; ++r) { cur.pb[s][r] = nxt.pb[s][r]; cur.pl[s][r] = nxt.pl[s][r]; }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (r * 64 + lane == Ub) score[b] = a[r] <= MONO_DEAD ? -INFINITY : (float)a[r];      // no terminal blank (a NaN stays a NaN)
+    if (!backtrace) return;          // measurement only (ttmi_set_option(23, 2)): the forward walk alone
+    if constexpr (!LDS_DEC) __threadfence();
+    __syncthreads();                 // lane 0's decision words are visible to the whole wave
+    int t = Tb - 1, u = Ub;          // the move into (t + 1, u) is frame t's decision
+    while (t >= 0) {
+        const int g = u >> 6;
+        const int tl = t - lane;
+        dec_t w = 0;
+        if (tl >= 0) {
+            if constexpr (LDS_DEC) w = dec_l[tl * W + g];
+            else w = dec_g[(long)tl * W + g];
+        }
+        const int wlo = (int)(unsigned)(w & 0xffffffffULL), whi = (int)(unsigned)(w >> 32);
+        for (int j = 0; j < 64 && t >= 0 && (u >> 6) == g; ++j, --t) {
+            const unsigned lo = (unsigned)__builtin_amdgcn_readlane(wlo, j), hi = (unsigned)__builtin_amdgcn_readlane(whi, j);
+            const unsigned bit = (((u & 32) ? hi : lo) >> (u & 31)) & 1u;
+            if (u > 0 && (bit || u > t)) {      // (t, u - 1) -> (t + 1, u): label u is frame t's decision (forced once u = t + 1 labels are left)
+                if (lane == 0) fr[u - 1] = t;
+                --u;
+            }
+        }
+    }
+}
+
+// Per label, the posterior over its emission frame from a finished forward: e(t,u) = exp(alpha(t,u) + lpl(t,u) + beta(t+1,u+1) - ll), u < U_b.
+// mass = sum_t e (every path emits every label exactly once: 1, a health check of the lattice), expected = sum_t t e.  One workgroup per
+// (utterance, 64 labels): lanes across u, so every load of the time-major tables is one coalesced row segment; wave w takes frames w,
+// w + MONO_ES_WAVES, ... in order, and the partial sums meet in LDS, added by wave 0 in wave order - fp64 throughout, the same order in
+// every run, no atomics.  Entries u >= U_b and utterances without a path: mass 0, expected -1.
+constexpr int MONO_ES_WAVES = 16;
+
+__global__ __launch_bounds__(MONO_ES_WAVES * 64) void mono_emit_stats_kernel(
+    const acc_t* __restrict__ alpha_g, const acc_t* __restrict__ beta_g, const acc_t* __restrict__ ll, const float* __restrict__ lpl_g,
+    const int* __restrict__ act_lens, const int* __restrict__ label_lens, int T, int U1, int G, float* __restrict__ expected,
+    float* __restrict__ mass) {
+    __shared__ acc_t part[2][MONO_ES_WAVES][64];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.x / G;
+    const int u = (blockIdx.x % G) * 64 + lane;
+    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U1 - 1);
+    const acc_t L = ll[b];
+    const bool live = !(Ub > Tb) && !(L <= MONO_DEAD);      // wave-uniform
+    acc_t m = 0.0, e1 = 0.0;
+    if (live && u < Ub) {
+        const acc_t* al = alpha_g + (long)b * (T + 1) * U1 + u;
+        const acc_t* be = beta_g + (long)b * (T + 1) * U1 + U1 + u + 1;      // beta(t + 1, u + 1)
+        const float* pl = lpl_g + (long)b * T * U1 + u;
+#pragma unroll 4
+        for (int t = wv; t < Tb; t += MONO_ES_WAVES) {
+            const long o = (long)t * U1;
+            const acc_t e = (acc_t)__expf((float)(al[o] + (acc_t)pl[o] + be[o] - L));
+            m += e;
+            e1 += (acc_t)t * e;
+        }
+    }
+    part[0][wv][lane] = m;
+    part[1][wv][lane] = e1;
+    __syncthreads();
+    if (wv == 0 && u < U1 - 1) {
+        m = part[0][0][lane];
+        e1 = part[1][0][lane];
+#pragma unroll
+        for (int k = 1; k < MONO_ES_WAVES; ++k) {
+            m += part[0][k][lane];
+            e1 += part[1][k][lane];
+        }
+        const bool has = live && u < Ub;
+        mass[(long)b * (U1 - 1) + u] = has ? (float)m : 0.f;
+        expected[(long)b * (U1 - 1) + u] = has ? (float)e1 : -1.f;
+    }
+}
+
+constexpr size_t MONO_VIT_LDS_MAX = 128 * 1024;      // rnnt.hip's VIT_LDS_MAX: decision words of one utterance kept in LDS up to here (of the CU's 160 KB)
+__host__ __device__ __forceinline__ size_t mono_dec_bytes(int T, int U1) { return (size_t)T * ((U1 + 63) / 64) * sizeof(dec_t); }
+
+template <int R, int PF>
+int mono_launch_viterbi(hipStream_t st, int B, const MonoWs& w, const int* al, const int* ll_, int T, int U1, dec_t* dec_ws, int* frames,
+                        float* score, int debug) {
+    const int W = (U1 + 63) / 64;
+    const size_t lds = mono_dec_bytes(T, U1);
+    const int backtrace = (debug & 2) ? 0 : 1;
+    if (lds <= MONO_VIT_LDS_MAX && !(debug & 1)) {
+        if (lds > 64 * 1024) {
+            // above the default limit the attribute is needed, and it belongs to the current DEVICE: it is set on every such call (a host-side
+            // call, no stream work) instead of being remembered per process
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mono_viterbi_kernel<R, PF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MONO_VIT_LDS_MAX);
+            if (e != hipSuccess) {
+                ttmi_set_error("mono align: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
+                return (int)e;
+            }
+        }
+        hipLaunchKernelGGL((mono_viterbi_kernel<R, PF, true>), dim3(B), dim3(64), lds, st, w.lpb, w.lpl, al, ll_, T, U1, W, dec_ws, frames, score, backtrace);
+    } else {
+        hipLaunchKernelGGL((mono_viterbi_kernel<R, PF, false>), dim3(B), dim3(64), 0, st, w.lpb, w.lpl, al, ll_, T, U1, W, dec_ws, frames, score, backtrace);
+    }
+    return TTMI_OK;
+}
+
 }  // namespace
 
+int ttmi_rnnt_get_align_debug();          // rnnt.hip: ttmi_set_option(23, bits), shared with ttmi_rnnt_align
+
 extern "C" {
+
+// Forced alignment and emission statistics from the workspace a finished ttmi_mono_loss_fwd left on the same (B, T, U1); that workspace is
+// only read (include/ttmi.h).  No host synchronisation, no memset node: both are capturable in a HIP graph.
+size_t ttmi_mono_align_workspace_bytes(int B, int T, int U1) {
+    if (B <= 0 || T <= 0 || U1 <= 0) return 0;
+    return (size_t)B * mono_dec_bytes(T, U1);
+}
+
+int ttmi_mono_align(const void* workspace, const int* act_lens, const int* label_lens, int B, int T, int U1, void* align_workspace,
+                    int* frames, float* score, void* stream) {
+    TTMI_REQUIRE(workspace && act_lens && label_lens && align_workspace && (frames || U1 == 1) && score, "mono_align: null pointer");
+    TTMI_REQUIRE(B > 0 && T > 0 && U1 > 0, "mono_align: bad shape B=%d T=%d U1=%d", B, T, U1);
+    TTMI_REQUIRE(U1 <= 1024, "mono_align: U+1=%d > 1024 unsupported", U1);
+    TTMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0 && (reinterpret_cast<uintptr_t>(align_workspace) & 7) == 0,
+                 "mono_align: workspaces must be 8-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const MonoWs w = mono_carve(const_cast<void*>(workspace), B, T, U1);
+    dec_t* dec = static_cast<dec_t*>(align_workspace);
+    const int debug = ttmi_rnnt_get_align_debug();
+    int rc;
+    if (U1 <= 64) rc = mono_launch_viterbi<1, 8>(st, B, w, act_lens, label_lens, T, U1, dec, frames, score, debug);
+    else if (U1 <= 128) rc = mono_launch_viterbi<2, 8>(st, B, w, act_lens, label_lens, T, U1, dec, frames, score, debug);
+    else if (U1 <= 256) rc = mono_launch_viterbi<4, 4>(st, B, w, act_lens, label_lens, T, U1, dec, frames, score, debug);
+    else if (U1 <= 512) rc = mono_launch_viterbi<8, 2>(st, B, w, act_lens, label_lens, T, U1, dec, frames, score, debug);
+    else rc = mono_launch_viterbi<16, 1>(st, B, w, act_lens, label_lens, T, U1, dec, frames, score, debug);
+    if (rc) return rc;
+    TTMI_LAUNCH_CHECK("mono_viterbi_kernel");
+    return TTMI_OK;
+}
+
+int ttmi_mono_emit_stats(const void* workspace, const int* act_lens, const int* label_lens, int B, int T, int U1, float* expected,
+                         float* mass, void* stream) {
+    TTMI_REQUIRE(workspace && act_lens && label_lens && ((expected && mass) || U1 == 1), "mono_emit_stats: null pointer");
+    TTMI_REQUIRE(B > 0 && T > 0 && U1 > 0, "mono_emit_stats: bad shape B=%d T=%d U1=%d", B, T, U1);
+    TTMI_REQUIRE(U1 <= 1024, "mono_emit_stats: U+1=%d > 1024 unsupported", U1);
+    TTMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "mono_emit_stats: workspace must be 8-byte aligned");
+    if (U1 == 1) return TTMI_OK;          // no labels: nothing to write
+    const MonoWs w = mono_carve(const_cast<void*>(workspace), B, T, U1);
+    const int G = (U1 - 1 + 63) / 64;
+    hipLaunchKernelGGL(mono_emit_stats_kernel, dim3((unsigned)((long)B * G)), dim3(MONO_ES_WAVES * 64), 0, static_cast<hipStream_t>(stream), w.alpha,
+                       w.beta, w.ll, w.lpl, act_lens, label_lens, T, U1, G, expected, mass);
+    TTMI_LAUNCH_CHECK("mono_emit_stats_kernel");
+    return TTMI_OK;
+}
 
 // bytes of caller-provided workspace shared by ttmi_mono_loss_fwd / _bwd (8-byte aligned)
 size_t ttmi_mono_workspace_bytes(int B, int T, int U1) {

@@ -998,6 +998,7 @@ Ws carve(void* ws, int B, int T, int U1) {
 
 void ttmi_rnnt_set_lattice_version(int v) { g_lattice_version = v; }
 void ttmi_rnnt_set_align_debug(int v) { g_align_debug = v; }
+int ttmi_rnnt_get_align_debug() { return g_align_debug; }      // mono.hip: ttmi_mono_align honours the same bits
 static bool fastemit_ok(float lambda) { return __builtin_isfinite(lambda) && lambda >= 0.f; }
 void ttmi_probe_begin(int point, hipStream_t st);      // optim.hip: HIP-event timing probes (point 1 = loss forward, 2 = loss backward)
 void ttmi_probe_end(int point, hipStream_t st);

@@ -285,14 +285,18 @@ class _CTCHeadLossFn(torch.autograd.Function):
         return (denc * gout, *rets, None, None, None, None, None, None, None)
 
 
-def _joint_align(joint, enc, dec, labels, act_lens, label_lens, prec, chunk, blank, exp_state, stats):
+def _joint_align(joint, enc, dec, labels, act_lens, label_lens, prec, chunk, blank, exp_state, stats, topology="rnnt"):
     """joint network + loss forward + forced alignment, forward only, chunked over utterances as _JointLossFn.forward chunks: per chunk
     ttmi_joint_fwd + ttmi_rnnt_loss_fwd + ttmi_rnnt_align (+ ttmi_rnnt_emit_stats), or, with `exp_state` (the JointNet's _ExpShift) valid
     and the sizes supported, ttmi_joint_fwd_exp + ttmi_rnnt_loss_fwd_exp + the same two calls; the chunk's logits / P buffer is dropped
     before the next chunk.  The exp-domain form leaves the training state alone: it only READS exp_state.cur (and only when the state is
     valid), passes no shift_next and raises a flag of its own; chunks whose flag came back set are run again in the plain form (one host
-    read per call).  -> warprnnt_pytorch.AlignResult"""
+    read per call).  topology='monotonic': per chunk ttmi_joint_fwd + ttmi_mono_loss_fwd + ttmi_mono_align (+ ttmi_mono_emit_stats) on the
+    one-decision-per-frame lattice; that lattice has no exp-domain branch.  -> warprnnt_pytorch.AlignResult"""
     from warprnnt_pytorch import AlignResult
+    mono = ops.check_topology(topology) == "monotonic"
+    if mono and exp_state is not None:
+        raise ValueError("topology='monotonic' has no exp-domain form")
     with torch.no_grad():
         enc, dec = enc.detach().contiguous(), dec.detach().contiguous()
         wf, bf, wp, bp = (t.detach() for t in (joint.forward_layer.weight, joint.forward_layer.bias, joint.project_layer.weight,
@@ -313,8 +317,17 @@ def _joint_align(joint, enc, dec, labels, act_lens, label_lens, prec, chunk, bla
             c0 = starts[i]
             c1 = min(B, c0 + chunk)
             n = c1 - c0
-            ws = ops.rnnt_workspace(n, T, U1, dev)
             lab, al, ll = labels[c0:c1], act_lens[c0:c1], label_lens[c0:c1]
+            if mono:
+                ws = ops.mono_workspace(n, T, U1, dev)
+                logits, saved = ops.joint_fwd(enc[c0:c1], dec[c0:c1], wf, bf, wp, bp, prec)
+                cost[c0:c1] = ops.mono_loss_fwd(logits, lab, al, ll, blank, ws)
+                del logits, saved
+                frames[c0:c1], score[c0:c1] = ops.mono_align(ws, al, ll, n, T, U1)
+                if stats:
+                    expected[c0:c1], mass[c0:c1] = ops.mono_emit_stats(ws, al, ll, n, T, U1)
+                return
+            ws = ops.rnnt_workspace(n, T, U1, dev)
             if exp:
                 P, rowsum, saved, emis = ops.joint_fwd_exp(enc[c0:c1], dec[c0:c1], wf, bf, wp, bp, prec, exp_state.cur, lab.contiguous(), blank)
                 cost[c0:c1] = ops.rnnt_loss_fwd_exp(P, rowsum, lab, al, ll, blank, ws, exp_state.cur, None, emis, flags[i:i + 1])
@@ -460,15 +473,20 @@ class DeferredLogits(torch.Tensor):
                                   j.project_layer.bias, labels, act_lens, label_lens, self._prec, int(chunk), reduction,
                                   j.exp_shift_state(self._enc.device) if exp else None, grad, int(blank), fastemit_lambda)
 
-    def rnnt_align(self, labels, act_lens, label_lens, blank=0, *, stats=False):
+    def rnnt_align(self, labels, act_lens, label_lens, blank=0, *, stats=False, topology="rnnt"):
         """forced alignment on this handle's logits without forming them (called by warprnnt_pytorch.rnnt_align; arguments already
         certified there): the chunked forward-only loop of Transducer.align.  None when the handle was already used as a tensor (the
-        caller then aligns the real logits)."""
+        caller then aligns the real logits).  topology='monotonic': the same loop on the one-decision-per-frame lattice, in the plain
+        chunk form at the memory form's chunk size (no exp-domain branch)."""
         if self._real is not None:
             return None
         j = self._joint
         B, T, U1 = self.shape[0], self.shape[1], self.shape[2]
         ops.weights_fresh()
+        if ops.check_topology(topology) == "monotonic":
+            chunk = j.default_loss_chunk(B, T, U1, False, self._prec)
+            return _joint_align(j, self._enc, self._dec, labels, act_lens, label_lens, self._prec, int(chunk), int(blank), None, stats,
+                                "monotonic")
         exp = self._prec == 1 and os.environ.get("TTMI_DEFERRED_EXP", "1") != "0"
         st = j.exp_shift_state(self._enc.device) if exp else None
         exp = exp and st.valid
@@ -520,7 +538,9 @@ details=False returns), `frames` (list of int, the frame at which each token was
 log P(token) on its emission frame) and `score` (float): the log-probability of the decisions the greedy decoder took, one term per frame of the
 utterance - blank's log-probability against the label state current at that frame on a frame that does not emit, the token's on a frame that does.
 That is the path of this decoder (at most one symbol per frame, the emitting frame is consumed), NOT a path of the RNN-T lattice, which follows a
-label with a blank on the same frame: `score` is not comparable with `Transducer.align(...).score`.
+label with a blank on the same frame: `score` is not comparable with `Transducer.align(...).score` on the default topology.  It IS a path of the
+monotonic lattice: `Transducer.align_monotonic(inputs, ..., tokens, ...).score` is its upper bound, and equal to it where `frames` are
+the aligned frames.
 Beam decoding (beam_decode_batch / recognize_nbest) returns lists of the same type on the same probability model: there `score` is the log of the summed
 probability of every decision sequence the beam kept for `tokens` (hypotheses spelling the same tokens are merged), `frames` and `logprobs` those of the
 best single one of them."""
@@ -923,7 +943,9 @@ class Transducer(nn.Module):
 
         The encoders run under no_grad in whatever mode the module is in: call it in eval() mode.  On a module in train() with
         dropout > 0 the alignment is taken on dropped-out encoder states and the call draws from the dropout generator like any other
-        forward, so "does not disturb training" is a statement about the shift state only."""
+        forward, so "does not disturb training" is a statement about the shift state only.
+
+        This is the standard lattice; `align_monotonic` is the same call on the one-decision-per-frame lattice of the decoders."""
         from warprnnt_pytorch import check_lengths as certify
         labels, al, ll = (t.to(dtype=torch.int32) for t in (targets, inputs_length, targets_length))
         certify(labels.contiguous(), al.contiguous(), ll.contiguous(), inputs.shape[0], 0, targets.shape[1] + 1, False)
@@ -942,6 +964,33 @@ class Transducer(nn.Module):
         if chunk is None:
             chunk = self.default_loss_chunk(B, T, U1, st is not None)
         return _joint_align(self.joint, enc_state, dec_state, labels, al, ll, prec, int(chunk), 0, st, stats)
+
+    def align_monotonic(self, inputs, inputs_length, targets, targets_length, chunk=None, check_lengths=True, *, stats=False):
+        """`align` on the one-decision-per-frame lattice that loss(topology='monotonic') trains and that recognize / decode_batch / the beam
+        search walk (include/ttmi.h, ttmi_mono_align): per chunk joint_fwd -> mono_loss_fwd -> mono_align (-> mono_emit_stats), forward
+        only, under no_grad, at the chunk size of `loss()`'s plain form.  -> warprnnt_pytorch.AlignResult with the fields of `align`, where
+        `frames` is STRICTLY increasing (frames[b][u] = the frame whose ONE decision is label u+1), `score` has no terminal blank and is
+        comparable with DecodeResult.score - an upper bound of it for the same tokens - and `cost` is what
+        loss(reduction='none', topology='monotonic') returns.  Same tie rule.  There is no exp_domain argument: this lattice has no
+        exp-domain form.  Under check_lengths an utterance with more labels than frames is a ValueError; with the check off it has score
+        -inf, cost +inf, every frames / expected_frames entry -1 and mass 0.  (A method of its own and not a keyword of `align`, whose
+        parameter list is pinned; warprnnt_pytorch.rnnt_align takes topology='monotonic' for the same alignment on logits or a handle.)"""
+        from warprnnt_pytorch import check_lengths as certify, check_monotonic_lengths as monotonic_lengths
+        labels, al, ll = (t.to(dtype=torch.int32) for t in (targets, inputs_length, targets_length))
+        certify(labels.contiguous(), al.contiguous(), ll.contiguous(), inputs.shape[0], 0, targets.shape[1] + 1, False)
+        if not inputs.is_cuda:
+            raise ValueError("Transducer.align_monotonic: inputs must live on the GPU (the MI355X build has no CPU path)")
+        with torch.no_grad():
+            enc_state, dec_state = self._encode(inputs, targets)
+        B, T, U1 = enc_state.shape[0], enc_state.shape[1], dec_state.shape[1]
+        labels, al, ll = (t.to(device=enc_state.device).contiguous() for t in (labels, al, ll))
+        certify(labels, al, ll, B, T, U1, check_lengths)
+        if check_lengths:
+            monotonic_lengths(al, ll)                # ValueError for an utterance with more labels than frames
+        ops.weights_fresh()
+        if chunk is None:
+            chunk = self.default_loss_chunk(B, T, U1, False)
+        return _joint_align(self.joint, enc_state, dec_state, labels, al, ll, default_precision(), int(chunk), 0, None, stats, "monotonic")
 
     def default_loss_chunk(self, B, T, U1, exp_domain=False):
         """utterances per chunk of `loss()` (JointNet.default_loss_chunk)"""

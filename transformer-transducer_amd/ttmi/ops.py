@@ -175,6 +175,36 @@ def mono_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_o
     return grad
 
 
+def mono_align(workspace, act_lens, label_lens, B, T, U1):
+    """rnnt_align on the monotonic lattice: the best path through the lattice a finished mono_loss_fwd left in `workspace` (read only) ->
+    (frames int32 [B, U1-1]: the frame whose one decision is label u+1, STRICTLY increasing, -1 for u >= U_b; score f32 [B]: the path's
+    log-probability, -inf with all frames -1 for an utterance with more labels than frames).  The label move is taken only when strictly
+    greater (a tie goes to blank); include/ttmi.h, ttmi_mono_align"""
+    _need_cuda(workspace, act_lens, label_lens)
+    _trace("mono_align", B, T, U1)
+    f = lib().ttmi_mono_align_workspace_bytes
+    f.restype = ctypes.c_size_t
+    aws = torch.empty((f(c_int(B), c_int(T), c_int(U1)) + 7) // 8, dtype=torch.int64, device=workspace.device)
+    frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=workspace.device)
+    score = torch.empty(B, dtype=torch.float32, device=workspace.device)
+    check(lib().ttmi_mono_align(_p(workspace), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U1), _p(aws), _p(frames), _p(score),
+                                _stream()), "ttmi_mono_align")
+    return frames, score
+
+
+def mono_emit_stats(workspace, act_lens, label_lens, B, T, U1):
+    """rnnt_emit_stats on the monotonic lattice, from the alpha / beta of a finished mono_loss_fwd in `workspace` (read only) -> (expected
+    f32 [B, U1-1]: expected emission frame, -1 for u >= U_b; mass f32 [B, U1-1]: total emission posterior, 1 for a healthy lattice, 0 for
+    u >= U_b); an utterance without a path has 0 / -1 in every entry"""
+    _need_cuda(workspace, act_lens, label_lens)
+    _trace("mono_emit_stats", B, T, U1)
+    expected = torch.empty(B, U1 - 1, dtype=torch.float32, device=workspace.device)
+    mass = torch.empty(B, U1 - 1, dtype=torch.float32, device=workspace.device)
+    check(lib().ttmi_mono_emit_stats(_p(workspace), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U1), _p(expected), _p(mass),
+                                     _stream()), "ttmi_mono_emit_stats")
+    return expected, mass
+
+
 TOPOLOGIES = ("rnnt", "monotonic")
 
 

@@ -22,7 +22,8 @@ csrc/mono.hip, recursion in include/ttmi.h).  FastEmit is not built on it.
 `rnnt_align` (no counterpart in warp-transducer, which returns costs only) is
 forced alignment on the same arguments: the best path through the lattice
 (frame of every label's emission), its log-probability, the cost, and on
-request the expected emission frame of every label.
+request the expected emission frame of every label.  It takes `topology` too:
+on the monotonic lattice the emission frames are strictly increasing.
 """
 import os
 import weakref
@@ -195,7 +196,12 @@ class AlignResult(NamedTuple):
     """frames int32 [B, U]: frames[b][u] = the frame at which label u+1 of utterance b is emitted on the best path (the path's move
     (t, u) -> (t, u+1)), non-decreasing in u, -1 for u >= U_b; score f32 [B]: log-probability of that path; cost f32 [B]: -log P(y|x), the
     bits RNNTLoss(reduction='none') returns; with stats=True expected_frames f32 [B, U] (posterior mean emission frame, -1 for u >= U_b) and
-    mass f32 [B, U] (total emission posterior of the label: 1 for a healthy lattice, 0 for u >= U_b), else None"""
+    mass f32 [B, U] (total emission posterior of the label: 1 for a healthy lattice, 0 for u >= U_b), else None.
+
+    With topology='monotonic' the same five fields on the one-decision-per-frame lattice: frames[b][u] = the frame whose ONE decision is
+    label u+1 (the move (t, u) -> (t+1, u+1)), STRICTLY increasing in u; score has no terminal blank; cost holds the bits
+    RNNTLoss(reduction='none', topology='monotonic') returns; an utterance with more labels than frames has score -inf, cost +inf, every
+    frames / expected_frames entry -1 and mass 0"""
     frames: torch.Tensor
     score: torch.Tensor
     cost: torch.Tensor
@@ -203,26 +209,43 @@ class AlignResult(NamedTuple):
     mass: Optional[torch.Tensor] = None
 
 
-def rnnt_align(acts, labels, act_lens, label_lens, blank=0, check_lengths=None, *, stats=False):
+def rnnt_align(acts, labels, act_lens, label_lens, blank=0, check_lengths=None, *, stats=False, topology="rnnt"):
     """Forced alignment: arguments as rnnt_loss -> AlignResult.  Forward only (runs under no_grad).  Tie rule: a label move is taken only
     when strictly better than the blank move (include/ttmi.h, ttmi_rnnt_align).  A DeferredLogits handle goes through the fused joint +
-    loss path instead of being materialised, as in rnnt_loss."""
+    loss path instead of being materialised, as in rnnt_loss.
+
+    topology: 'rnnt' (the default: the standard lattice, the code and bits of before) or 'monotonic', the one-decision-per-frame lattice
+    of RNNTLoss(topology='monotonic') and of the decoders (include/ttmi.h, ttmi_mono_align): `frames` is then STRICTLY increasing, `score`
+    is comparable with the decoders' DecodeResult.score, and under check_lengths an utterance with more labels than frames is a
+    ValueError."""
+    mono = ops.check_topology(topology) == "monotonic"
     if check_lengths is None:
         check_lengths = os.environ.get("TTMI_CHECK_LENGTHS", "1") != "0"
     labels, act_lens, label_lens = (t.to(acts.device) for t in (labels, act_lens, label_lens))
     _certify(acts, labels, act_lens, label_lens, check_lengths)
     if not acts.is_cuda:
         raise ValueError("rnnt_align: acts must live on the GPU (the MI355X build has no CPU path)")
+    if mono and check_lengths:
+        check_monotonic_lengths(act_lens, label_lens)
     with torch.no_grad():
         fused = getattr(acts, "rnnt_align", None)
         if fused is not None:
-            out = fused(labels, act_lens, label_lens, int(blank), stats=bool(stats))
+            out = fused(labels, act_lens, label_lens, int(blank), stats=bool(stats), topology="monotonic") if mono else \
+                fused(labels, act_lens, label_lens, int(blank), stats=bool(stats))
             if out is not None:
                 return out
             acts = acts.materialize()
         acts = acts.detach()
         B, T, U1, _ = acts.shape
         acts_c = acts if ops.row_pitch(acts) is not None else acts.contiguous()
+        if mono:
+            ws = ops.mono_workspace(B, T, U1, acts.device)
+            cost = ops.mono_loss_fwd(acts_c, labels, act_lens, label_lens, int(blank), ws)
+            frames, score = ops.mono_align(ws, act_lens, label_lens, B, T, U1)
+            expected = mass = None
+            if stats:
+                expected, mass = ops.mono_emit_stats(ws, act_lens, label_lens, B, T, U1)
+            return AlignResult(frames, score, cost, expected, mass)
         ws = ops.rnnt_workspace(B, T, U1, acts.device)
         cost = ops.rnnt_loss_fwd(acts_c, labels, act_lens, label_lens, int(blank), ws)
         frames, score = ops.rnnt_align(ws, act_lens, label_lens, B, T, U1)
