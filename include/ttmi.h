@@ -293,6 +293,45 @@ int ttmi_mono_align(const void* workspace /* filled by ttmi_mono_loss_fwd on the
 int ttmi_mono_emit_stats(const void* workspace, const int* act_lens, const int* label_lens, int B, int T, int U1,
                          float* expected, float* mass, void* stream);
 
+/* ---- transducer knowledge distillation on collapsed lattice posteriors (Panchapagesan et al., ICASSP 2021; no reference counterpart) -----
+ * The distribution of every lattice node over the V outputs is collapsed to three classes - blank, the next label y_{u+1}, everything else -
+ * and the student is trained with the KL divergence from the teacher's three probabilities to its own.  The teacher hands over three floats
+ * per node instead of V logits, and need not share the student's V.  Arguments as for ttmi_mono_loss_fwd / _bwd: logits [B,T,U1,V] (dtype
+ * 0 = f32, 1 = bf16), row pitch ldv >= V; labels i32 [B,U1-1], clamped to [0, V-1]; act_lens, label_lens i32 [B], T_b clamped to [1, T],
+ * U_b to [0, U1-1]; blank in [0, V); V >= 2.  For a node (t, u), t < T_b, u <= U_b, with s = softmax(z[b,t,u,:]) and y = labels[b][u]; the
+ * label class is EMPTY when u == U_b or y == blank:
+ *     lb = z[blank] - lse          ly = z[y] - lse (NEG = -1e30 for an empty label class)          lo = lse(z[k], k not in {blank, y}) - lse
+ * lo is a log-sum-exp of its own over the other columns, taken in the same online pass; the row's lse is that sum joined with the two columns
+ * left out.  It is never formed as 1 - p_b - p_y, which loses the other mass of a confident row to cancellation.  Every collapsed
+ * log-probability is clamped below at NEG; an empty class holds NEG.
+ * ttmi_kd_collapse (the teacher's call): post f32 [B,T,U1,3] = (lb, ly, lo); rows outside the ragged lattice are exact zeros.
+ * ttmi_kd_loss_fwd (the student's): teacher f32 [B,T,U1,3] as ttmi_kd_collapse wrote it - the caller's contract is entries <= 0, or NEG for
+ * an empty class; P^T_c = exp(teacher_c), and P^T_y is taken as 0 where the student's label class is empty.
+ *     kd(t,u)  = sum_c P^T_c (log P^T_c - log P^S_c)                a class with P^T_c == 0 adds exactly 0
+ *     costs[b] = sum of kd over the utterance's nodes, fp64, in an order fixed by the shape (a second small launch), no atomics
+ * A NaN teacher entry makes its utterance's cost NaN; no index depends on a teacher value.  Per row the workspace keeps one 16-byte record
+ * (lse, c_o, P^T_b, P^T_y), c_o = P^T_o / P^S_o = exp(teacher_o - lo), 0 when the other class is empty on either side, and one f32 row cost.
+ * ttmi_kd_loss_bwd, with g = scale * grad_out[b * grad_out_stride]:
+ *     d z[k] = g * ( s_k - P^T_b )             k == blank
+ *              g * ( s_k - P^T_y )             k == y, label class not empty
+ *              g * s_k (1 - c_o)               otherwise
+ * Every row sums to zero when the teacher's three probabilities sum to one.  accumulate = 0: grad (the logits' dtype, pitch ldg) is written;
+ * rows outside the lattice and columns [V, ldg) are zeros; grad may alias logits when ldg == ldv.  accumulate = 1: the gradient is ADDED to
+ * what grad holds, over the lattice's rows and columns [0, V) - widened to f32, added, rounded once - and no other byte of grad is touched;
+ * aliasing the logits is TTMI_EINVAL.  workspace: ttmi_kd_workspace_bytes(B, T, U1) bytes, 16-byte aligned; the forward fills it, the
+ * backward reads it.  One wave per row, the 16-byte row walk of the monotonic loss, any pitch >= V.  No allocation, host synchronisation,
+ * memset node or floating-point atomic: every call may be captured in a HIP graph, and two runs give the same bits.  rc < 0 with a
+ * ttmi_last_error text, before any launch, on a null pointer or V < 2. */
+size_t ttmi_kd_workspace_bytes(int B, int T, int U1);
+int ttmi_kd_collapse(const void* logits, int dtype, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                     int B, int T, int U1, int V, int blank, float* post /* [B,T,U1,3] */, void* stream);
+int ttmi_kd_loss_fwd(const void* logits, int dtype, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                     int B, int T, int U1, int V, int blank, const float* teacher /* [B,T,U1,3] */, void* workspace, float* costs,
+                     void* stream);
+int ttmi_kd_loss_bwd(const void* logits, int dtype, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                     int B, int T, int U1, int V, int blank, const void* workspace, const float* grad_out,
+                     int grad_out_stride, float scale, void* grad, long ldg, int accumulate, void* stream);
+
 /* ---- grouped weight gradients (data-parallel hot path): the four weight-gradient GEMMs of an encoder layer are a quarter
  * of the chip each step; deferred and launched four layers at a time they are 256 tiles, one per CU over the whole reduction - no split along
  * K, no atomics, bit-identical from run to run and across ranks.  ttmi_attn_bwd_defer / ttmi_ffn_bwd_defer are ttmi_attn_bwd / ttmi_ffn_bwd

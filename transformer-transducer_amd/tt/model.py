@@ -122,7 +122,7 @@ class _JointLossFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, enc, dec, wf, bf, wp, bp, labels, act_lens, label_lens, prec, chunk, reduction, exp_state, grad_mode=True, blank=0,
-                fastemit_lambda=0.0, weights=None, topology="rnnt"):
+                fastemit_lambda=0.0, weights=None, topology="rnnt", distill=None, distill_weight=0.0):
         """exp_state: None (plain fused form) or the JointNet's _ExpShift for this device (exp-domain form); fastemit_lambda: the FastEmit
         weight of the loss gradient (warprnnt_pytorch.RNNTLoss), in all three chunk forms; weights: None or a constant f32 [B] on the device,
         one factor per utterance: the result is sum_b w_b cost_b (times 1 / B for 'mean') and every chunk's loss-gradient call reads its slice
@@ -130,11 +130,20 @@ class _JointLossFn(torch.autograd.Function):
         weights are all zero is NOT skipped: its costs are part of the result either way, and knowing that its weights are zero would take a
         host read of a device tensor - its gradient kernels run and add exact zeros; topology: 'rnnt', or 'monotonic' for the decoders'
         one-decision-per-frame lattice (ttmi_mono_loss_fwd / _bwd): that one has the plain chunk form only - joint_fwd, mono_loss_fwd,
-        mono_loss_bwd in place, joint_bwd - no exp-domain form, no pre-split gradient planes and no shift seeding"""
+        mono_loss_bwd in place, joint_bwd - no exp-domain form, no pre-split gradient planes and no shift seeding; distill (None, or with
+        distill_weight 0: the code path and bits without it): the teacher's collapsed lattice posteriors, a constant f32 [B, T, U1, 3] on the
+        device (ttmi.distill) - the result is the transducer term + distill_weight * KD under the same reduction (KD is not multiplied by
+        `weights`).  A chunk then runs joint_fwd, the topology's loss forward, kd_loss_fwd, the topology's loss gradient OUT of place (FastEmit
+        included; in the bf16x3 mode the f32 gradient goes through joint_bwd's own split pass, as on the monotonic lattice), kd_loss_bwd
+        adding scale * distill_weight * d KD onto that gradient, joint_bwd.  A second chunk buffer is alive meanwhile; the 2 GB budget of
+        default_loss_chunk leaves room for it, so the chunk size is the same.  No exp-domain form"""
         fe = ops.check_fastemit(fastemit_lambda)
         mono = ops.check_topology(topology, fe) == "monotonic"
         if mono and exp_state is not None:
             raise ValueError("topology='monotonic' has no exp-domain form")
+        kd = distill is not None and float(distill_weight) != 0.0
+        if kd and exp_state is not None:
+            raise ValueError("distill has no exp-domain form")
         enc, dec = enc.contiguous(), dec.contiguous()
         params = (wf, bf, wp, bp)
         wf_, bf_, wp_, bp_ = (t.detach() for t in params)
@@ -142,6 +151,7 @@ class _JointLossFn(torch.autograd.Function):
         U1 = dec.shape[1]
         need = grad_mode and any(ctx.needs_input_grad[:6])      # (needs_input_grad ignores torch.no_grad(); forward() itself always runs without grad mode)
         costs = torch.empty(B, dtype=torch.float32, device=enc.device)
+        kd_costs = torch.empty(B, dtype=torch.float32, device=enc.device) if kd else None
         one = torch.ones(1, dtype=torch.float32, device=enc.device)
         scale = 1.0 / B if reduction == "mean" else 1.0
         if need:
@@ -160,6 +170,22 @@ class _JointLossFn(torch.autograd.Function):
         for c0 in range(0, B, chunk):
             c1 = min(B, c0 + chunk)
             lab, al, ll = labels[c0:c1], act_lens[c0:c1], label_lens[c0:c1]
+            if kd:
+                ws = (ops.mono_workspace if mono else ops.rnnt_workspace)(c1 - c0, T, U1, enc.device)
+                kws = ops.kd_workspace(c1 - c0, T, U1, enc.device)
+                logits, saved = ops.joint_fwd(enc[c0:c1], dec[c0:c1], wf_, bf_, wp_, bp_, prec)
+                costs[c0:c1] = (ops.mono_loss_fwd if mono else ops.rnnt_loss_fwd)(logits, lab, al, ll, blank, ws)
+                kd_costs[c0:c1] = ops.kd_loss_fwd(logits, lab, al, ll, blank, distill[c0:c1], kws)
+                if need:
+                    if mono:
+                        grad = ops.mono_loss_bwd(logits, lab, al, ll, blank, ws, *upstream(c0, c1), scale, inplace=False)
+                    else:
+                        grad = ops.rnnt_loss_bwd(logits, lab, al, ll, blank, ws, *upstream(c0, c1), scale, inplace=False, fastemit_lambda=fe)
+                    grad = ops.kd_loss_bwd(logits, lab, al, ll, blank, kws, one, 0, scale * float(distill_weight), accumulate=grad)
+                    ops.joint_bwd(grad, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
+                    del grad
+                del logits, saved
+                continue
             if mono:
                 ws = ops.mono_workspace(c1 - c0, T, U1, enc.device)
                 logits, saved = ops.joint_fwd(enc[c0:c1], dec[c0:c1], wf_, bf_, wp_, bp_, prec)
@@ -206,6 +232,11 @@ class _JointLossFn(torch.autograd.Function):
         if need:
             ctx.save_for_backward(denc, ddec, *g.values())
         ctx.params = params
+        if kd:
+            if reduction == "none":
+                return costs + float(distill_weight) * kd_costs
+            total = (costs * weights).sum() if weights is not None else costs.sum()
+            return (total + float(distill_weight) * kd_costs.sum()).reshape(1) * scale
         if reduction == "none":
             return costs
         if weights is not None:
@@ -229,7 +260,7 @@ class _JointLossFn(torch.autograd.Function):
                     cb()
             else:
                 rets.append(gp * gout)
-        return (denc * gout, ddec * gout, *rets, None, None, None, None, None, None, None, None, None, None, None, None)
+        return (denc * gout, ddec * gout, *rets, None, None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
 class _CTCHeadLossFn(torch.autograd.Function):
@@ -597,7 +628,9 @@ class JointNet(nn.Module):
         step, two halves 36.2; C5's 28 GB in one chunk 102.0 ms, in two 104.2 - on 288 GB of HBM the budget is not the constraint).  The
         chunks are balanced (B = 33 at a budget of 32 gives 17 + 16, not 32 + 1: every chunk stays above the persistent kernels' minimum
         row count).  Any row count runs the exp-domain kernels: the library pads the wgrad's reduction to its 64-row tile (round 3 needed
-        chunk * T * U1 % 64 == 0 and fell back to the plain form otherwise - half of all real batches at B = 32)."""
+        chunk * T * U1 % 64 == 0 and fell back to the plain form otherwise - half of all real batches at B = 32).  With distillation
+        (`loss(distill=...)`) a second chunk buffer, the out-of-place gradient, is alive beside the logits; the 2 GB budget leaves room for it
+        and the chunk size is the same."""
         prec = default_precision() if prec is None else prec
         es = 2 if ops.joint_logits_dtype(prec, self.forward_layer.out_features) is torch.bfloat16 else 4
         budget = (32 << 30) if (exp_domain or prec == 2) else (2 << 30)     # (bf16x3: the speed form as well - C2 in eight chunks 108 ms, in one 93.4)
@@ -696,7 +729,7 @@ class Transducer(nn.Module):
         return self.joint(enc_state, dec_state)
 
     def loss(self, inputs, inputs_length, targets, targets_length, reduction="mean", chunk=None, check_lengths=True, exp_domain=False, *,
-             fastemit_lambda=0.0, ctc_weight=None, utterance_weights=None, topology="rnnt"):
+             fastemit_lambda=0.0, ctc_weight=None, utterance_weights=None, topology="rnnt", distill=None, distill_weight=0.0):
         """Opt-in fused form of train.py:51-53 (`logits = model(inputs, targets); loss = criterion(logits, targets.int(),
         inputs_length.int(), targets_length.int())`) that never materialises the logits (API precedent: tt_espnet/model.py:35-81 returns
         the loss from forward).  Same numbers as the two-call form: the same kernels run, one chunk of `chunk` utterances at a time
@@ -721,12 +754,27 @@ class Transducer(nn.Module):
 
         topology ('rnnt': today's code path and bits): 'monotonic' trains the one-decision-per-frame lattice the decoders of this class walk
         (warprnnt_pytorch.RNNTLoss has the same option) in the plain chunk form; ValueError together with exp_domain=True or
-        fastemit_lambda > 0, and, under check_lengths, for an utterance with more labels than frames."""
+        fastemit_lambda > 0, and, under check_lengths, for an utterance with more labels than frames.
+
+        distill, distill_weight (None, or a weight of 0: today's code path and bits): knowledge distillation from a teacher on collapsed
+        lattice posteriors (ttmi.distill).  `distill` is what the teacher's `lattice_posteriors` returned for the same batch, a constant f32
+        [B, T, U+1, 3] on the device; the call returns rnnt + distill_weight * KD with the reduction of the transducer term, KD being the KL
+        divergence from the teacher's (blank, next label, other) probabilities to the student's, summed over each utterance's lattice nodes.
+        Both topologies and FastEmit are supported.  Like the CTC term, the KD term is not multiplied by utterance_weights.  Per chunk the
+        transducer gradient is written out of place and the KD gradient added to it, so a second chunk buffer is alive meanwhile:
+        default_loss_chunk's 2 GB budget leaves room for it and the chunk size is unchanged.  ValueError together with exp_domain=True (the
+        collapsed classes have no exp-domain form), for a distill_weight that is not a finite number >= 0, and for a `distill` of another
+        shape, dtype or device."""
         from warprnnt_pytorch import check_lengths as certify, check_monotonic_lengths as monotonic_lengths
         fastemit_lambda = ops.check_fastemit(fastemit_lambda)
         mono = ops.check_topology(topology, fastemit_lambda) == "monotonic"
         if mono and exp_domain:
             raise ValueError("topology='monotonic' has no exp-domain form: leave exp_domain off")
+        distill_weight = self._distill_weight(distill_weight)
+        if distill is None or distill_weight == 0.0:
+            distill, distill_weight = None, 0.0
+        elif exp_domain:
+            raise ValueError("distill has no exp-domain form: leave exp_domain off")
         ctc_weight = self._ctc_weight(ctc_weight)
         if utterance_weights is not None:
             utterance_weights = self._utterance_weights(utterance_weights, inputs.shape[0], reduction)
@@ -741,6 +789,15 @@ class Transducer(nn.Module):
         if chunk is None:
             chunk = self.default_loss_chunk(B, T, U1, exp_domain)
         j = self.joint
+        if distill is not None:
+            from ttmi.distill import check_teacher
+            distill = check_teacher(distill, B, T, U1)
+            rnnt = _JointLossFn.apply(enc_state, dec_state, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
+                                      j.project_layer.bias, labels, al, ll, prec, int(chunk), reduction, None, torch.is_grad_enabled(), 0,
+                                      fastemit_lambda, utterance_weights, topology, distill, distill_weight)
+            if ctc_weight > 0.0:
+                return rnnt + ctc_weight * self._ctc_from_states(enc_state, labels, al, ll, reduction)
+            return rnnt
         rnnt = _JointLossFn.apply(enc_state, dec_state, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
                                   j.project_layer.bias, labels, al, ll, prec, int(chunk), reduction,
                                   j.exp_shift_state(enc_state.device) if exp_domain and prec == 1 else None, torch.is_grad_enabled(), 0,
@@ -748,6 +805,49 @@ class Transducer(nn.Module):
         if ctc_weight > 0.0:
             return rnnt + ctc_weight * self._ctc_from_states(enc_state, labels, al, ll, reduction)
         return rnnt
+
+    @staticmethod
+    def _distill_weight(w):
+        """-> distill_weight as a float; ValueError unless it is a finite number >= 0"""
+        try:
+            v = float(w)
+        except (TypeError, ValueError):
+            raise ValueError("distill_weight must be a finite float >= 0, got %r" % (w,)) from None
+        if not math.isfinite(v) or v < 0.0:
+            raise ValueError("distill_weight must be a finite float >= 0, got %r" % (w,))
+        return v
+
+    def lattice_posteriors(self, inputs, inputs_length, targets, targets_length, chunk=None, check_lengths=True):
+        """The teacher's call of knowledge distillation on collapsed lattice posteriors (ttmi.distill; `loss(distill=...)` is the student's):
+        -> f32 [B, T, U+1, 3], (log P(blank), log P(y_{u+1}), log P(anything else)) at every lattice node of (inputs, targets), exact zeros
+        outside the ragged lattice.  Under no_grad, without materialising the logits: per chunk of `loss()`'s plain form joint_fwd then
+        kd_collapse, and the chunk's logits are dropped before the next chunk.  12 bytes per node (9.8 MB for a whole C2 batch): it can be
+        computed once per utterance and cached.  The encoders run in whatever mode the module is in: call it in eval() mode."""
+        from warprnnt_pytorch import check_lengths as certify
+        labels, al, ll = (t.to(dtype=torch.int32) for t in (targets, inputs_length, targets_length))
+        certify(labels.contiguous(), al.contiguous(), ll.contiguous(), inputs.shape[0], 0, targets.shape[1] + 1, False)
+        if not inputs.is_cuda:
+            raise ValueError("Transducer.lattice_posteriors: inputs must live on the GPU (the MI355X build has no CPU path)")
+        with torch.no_grad():
+            enc_state, dec_state = self._encode(inputs, targets)
+            B, T, U1 = enc_state.shape[0], enc_state.shape[1], dec_state.shape[1]
+            labels, al, ll = (t.to(device=enc_state.device).contiguous() for t in (labels, al, ll))
+            certify(labels, al, ll, B, T, U1, check_lengths)
+            ops.weights_fresh()
+            prec = default_precision()
+            if chunk is None:
+                chunk = self.default_loss_chunk(B, T, U1, False)
+            chunk = int(chunk)
+            enc, dec = enc_state.detach().contiguous(), dec_state.detach().contiguous()
+            j = self.joint
+            wf, bf, wp, bp = (t.detach() for t in (j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight, j.project_layer.bias))
+            post = torch.empty(B, T, U1, 3, dtype=torch.float32, device=enc.device)
+            for c0 in range(0, B, chunk):
+                c1 = min(B, c0 + chunk)
+                logits, saved = ops.joint_fwd(enc[c0:c1], dec[c0:c1], wf, bf, wp, bp, prec)
+                post[c0:c1] = ops.kd_collapse(logits, labels[c0:c1], al[c0:c1], ll[c0:c1], 0)
+                del logits, saved
+        return post
 
     @staticmethod
     def _utterance_weights(w, B, reduction):

@@ -205,6 +205,94 @@ def mono_emit_stats(workspace, act_lens, label_lens, B, T, U1):
     return expected, mass
 
 
+# ----------------------------------------------------------------------------- distillation on collapsed lattice posteriors (csrc/distill.hip)
+def kd_workspace(B, T, U1, device):
+    f = lib().ttmi_kd_workspace_bytes
+    f.restype = ctypes.c_size_t
+    n = f(c_int(B), c_int(T), c_int(U1))
+    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+
+
+def _kd_args(logits, labels, act_lens, label_lens):
+    if logits.dim() != 4 or logits.dtype not in _DT or _DT[logits.dtype] > 1:
+        raise ValueError("kd: logits must be an f32 / bf16 tensor [B, T, U1, V]")
+    B, T, U1, V = logits.shape
+    if V < 2:
+        raise ValueError("kd: V = %d < 2 (a blank and at least one label)" % V)
+    ld = row_pitch(logits)
+    if ld is None:
+        raise ValueError("kd: logits must be dense or a row-padded [..., :V] view")
+    for name, t, shape in (("labels", labels, (B, U1 - 1)), ("act_lens", act_lens, (B,)), ("label_lens", label_lens, (B,))):
+        if t.dtype != torch.int32 or not t.is_contiguous() or (tuple(t.shape) != shape and not (name == "labels" and U1 == 1)):
+            raise ValueError("kd: %s must be a contiguous int32 tensor %s" % (name, list(shape)))
+    return B, T, U1, V, ld
+
+
+def _kd_post(t, name, B, T, U1):
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != (B, T, U1, 3):
+        raise ValueError("kd: %s must have shape [%d, %d, %d, 3]" % (name, B, T, U1))
+    if t.dtype != torch.float32:
+        raise ValueError("kd: %s must be float32, got %s" % (name, t.dtype))
+    if not t.is_cuda:
+        raise ValueError("kd: %s must live on the GPU (no CPU fallback)" % name)
+    return t.contiguous()
+
+
+def kd_collapse(logits, labels, act_lens, label_lens, blank=0):
+    """logits f32 / bf16 [B,T,U1,V], dense or row-padded view -> f32 [B,T,U1,3]: (log P(blank), log P(y_{u+1}), log P(anything else)) of every
+    lattice node, zeros outside the ragged lattice (include/ttmi.h, ttmi_kd_collapse)"""
+    _need_cuda(logits, labels, act_lens, label_lens)
+    B, T, U1, V, ld = _kd_args(logits, labels, act_lens, label_lens)
+    _trace("kd_collapse", B, T, U1, V)
+    post = torch.empty(B, T, U1, 3, dtype=torch.float32, device=logits.device)
+    check(lib().ttmi_kd_collapse(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
+                                 c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(post), _stream()), "ttmi_kd_collapse")
+    return post
+
+
+def kd_loss_fwd(logits, labels, act_lens, label_lens, blank, teacher, workspace):
+    """-> costs f32 [B]: the KL divergence from the teacher's collapsed posteriors (f32 [B,T,U1,3], as kd_collapse gives them) to the
+    student's, summed over each utterance's lattice nodes"""
+    _need_cuda(logits, labels, act_lens, label_lens, workspace)
+    B, T, U1, V, ld = _kd_args(logits, labels, act_lens, label_lens)
+    teacher = _kd_post(teacher, "teacher", B, T, U1)
+    _trace("kd_loss_fwd", B, T, U1, V)
+    costs = torch.empty(B, dtype=torch.float32, device=logits.device)
+    check(lib().ttmi_kd_loss_fwd(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
+                                 c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(teacher), _p(workspace), _p(costs), _stream()),
+          "ttmi_kd_loss_fwd")
+    return costs
+
+
+def kd_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, inplace=False, accumulate=None):
+    """accumulate=None: the gradient is written - over the logits (inplace, same dtype and pitch) or to a new buffer of the logits' pitch, as
+    in mono_loss_bwd.  accumulate=<tensor>: a gradient of the logits' shape and dtype (dense or row-padded) to which this one is ADDED over
+    the lattice's rows, columns [0, V); no other byte of it is touched; the library refuses the logits themselves (ValueError)"""
+    _need_cuda(logits, labels, act_lens, label_lens, workspace, grad_out, accumulate)
+    B, T, U1, V, ld = _kd_args(logits, labels, act_lens, label_lens)
+    if accumulate is not None:
+        if inplace:
+            raise ValueError("kd_loss_bwd: accumulate and inplace exclude each other")
+        if accumulate.shape != logits.shape or accumulate.dtype != logits.dtype or row_pitch(accumulate) is None:
+            raise ValueError("kd_loss_bwd: accumulate must have the logits' shape and dtype (dense or row-padded)")
+        grad, ldg = accumulate, row_pitch(accumulate)
+    elif inplace:
+        grad, ldg = logits, ld
+    elif ld == V:
+        grad, ldg = torch.empty_like(logits), V
+    else:
+        buf = torch.empty(B, T, U1, ld, dtype=logits.dtype, device=logits.device)
+        grad, ldg = buf[..., :V], ld
+    _trace("kd_loss_bwd", B, T, U1, V)
+    check(lib().ttmi_kd_loss_bwd(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
+                                 c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(grad_out),
+                                 c_int(grad_out_stride), c_float(scale), _p(grad), c_long(ldg), c_int(0 if accumulate is None else 1),
+                                 _stream()), "ttmi_kd_loss_bwd")
+    if accumulate is None and ldg != V:
+        grad._ttmi_zero_pad = ldg
+    return grad
+
+
 TOPOLOGIES = ("rnnt", "monotonic")
 
 
