@@ -498,6 +498,41 @@ int ttmi_beam_step_ctx(const void* logits, int dtype, long ld, int B, int W, int
                        int* parent, int* fresh, int S, int A, const int* arc_off, const int* arc_sym, const int* arc_next, const float* arc_w,
                        const int* fail, const float* fail_w, const int* state_in, const double* bias_in, int* state_out, double* bias_out,
                        void* ws, void* stream);
+/* Language-model fusion inside the beam step: ttmi_beam_step_fuse is ttmi_beam_step_ctx with dense external scores, the rows a neural
+ * language model (shallow fusion) or the label encoder's own prior (internal-LM subtraction) gives for every hypothesis.  Same launch shape
+ * and promises: one workgroup per utterance, no allocation, no host synchronisation, no memset node, capturable in a HIP graph, no
+ * floating-point atomics, two runs give the same bits.
+ * Arguments: ttmi_beam_step_ctx's, automaton included (a search without hotwords passes the trivial one: S = 1, A = 0, arc_off = {0, 0},
+ * fail = {0}, fail_w = {0}); ws holds ttmi_beam_fuse_ws_bytes(B, W, V) bytes.  Then the per-slot accumulator fuse_in / fuse_out f64 [B, W] in
+ * buffers of their own, double sym_bonus, and up to two sources j in {0, 1}: ext_j (device pointer, NULL = absent), ext_j_dtype (0 = f32,
+ * 1 = bf16), ext_j_ld >= V (row (b, w) starts at element (b * W + w) * ext_j_ld), double ext_j_w, int ext_j_norm.  Row (b, w) of a source
+ * belongs to the hypothesis of slot w and is a function of that slot's tokens alone, so the two sides of a merge carry the same fuse.
+ * Rule = ttmi_beam_step_ctx's rule with these changes and no others:
+ *  - Per live slot w and source j, lpx_j(w, k) = x_j[w][k] - L_j(w) in f32.  norm 0: L_j = 0 (the row holds log-probabilities; no pass is
+ *    made over it).  norm 1: L_j = the row's log-sum-exp over all V entries, in one f32 pass exactly as the main row's.  norm 2: the
+ *    log-sum-exp over all entries but the blank (the internal LM's renormalisation).  A row without a finite L_j has lpx_j = NaN throughout.
+ *  - e(w, k) = sym_bonus + ext_0_w * (double)lpx_0(w, k) + ext_1_w * (double)lpx_1(w, k), accumulated in f64 in that order, every product
+ *    and sum rounded on its own, absent sources skipped.
+ *  - The extension of i by k carries fuse' = fuse_i + e(i, k), state and bias' as before, key = score + (bias' + fuse').  The blank extension
+ *    of i carries fuse_i, key = score + (bias_i + fuse_i): the sources never touch it.
+ *  - A symbol candidate whose e is not finite (NaN, +-inf) takes no slot.  A NaN key counts as -inf, as before.
+ *  - A merged candidate takes i's state, bias and fuse (i's own stored values); which side's details it takes is decided by the two scores.
+ *  - A finished utterance copies fuse through; an empty new slot gets fuse 0.
+ * score_out stays the model's log-probability; bias_out is ttmi_beam_step_ctx's (the same f32 weights summed in the same order).  With both
+ * sources absent and sym_bonus = 0 every output ttmi_beam_step_ctx also has is bit-identical to its, and fuse_out is 0 where fuse_in is.
+ * The kernel reads a source row only for a live slot of an unfinished utterance.
+ * rc < 0 with a ttmi_last_error text before any launch on anything ttmi_beam_step_ctx refuses, a null fuse buffer, fuse_out == fuse_in, a
+ * non-finite sym_bonus, and per present source: a dtype outside 0..1, a norm outside 0..2, a non-finite weight, ext_j_ld < V, rows that
+ * overlap an output buffer (the new beam's arrays, parent, fresh, state_out, bias_out, fuse_out, ws). */
+size_t ttmi_beam_fuse_ws_bytes(int B, int W, int V);
+int ttmi_beam_step_fuse(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len,
+                        const double* score_in, const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in,
+                        double* score_out, int* len_out, long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det,
+                        int* parent, int* fresh, int S, int A, const int* arc_off, const int* arc_sym, const int* arc_next, const float* arc_w,
+                        const int* fail, const float* fail_w, const int* state_in, const double* bias_in, int* state_out, double* bias_out,
+                        void* ws, const double* fuse_in, double* fuse_out, double sym_bonus, const void* ext_0, int ext_0_dtype, long ext_0_ld,
+                        double ext_0_w, int ext_0_norm, const void* ext_1, int ext_1_dtype, long ext_1_ld, double ext_1_w, int ext_1_norm,
+                        void* stream);
 
 /* ---- error counting (ttmi.metrics: evaluation, and the per-hypothesis error counts of minimum word error rate training).
  * ttmi_edit_distance: token edit distance of P (hypothesis, transcript) pairs with its substitution / deletion / insertion counts.  One wave

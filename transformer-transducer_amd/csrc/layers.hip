@@ -1688,6 +1688,21 @@ int ttmi_beam_step_ctx(const void* logits, int dtype, long ld, int B, int W, int
                          hist_out, frames_out, tok_lp_out, ld_hist, ld_det, parent, fresh, S, A, arc_off, arc_sym, arc_next, arc_w, fail, fail_w,
                          state_in, bias_in, state_out, bias_out, ws, static_cast<hipStream_t>(stream));
 }
+// ... and with dense external scores: language-model fusion and internal-LM subtraction (Transducer.beam_decode_batch(lm=...), ttmi.h)
+size_t ttmi_beam_fuse_ws_bytes(int B, int W, int V) { return beam_fuse_ws_bytes(B, W, V); }
+int ttmi_beam_step_fuse(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len,
+                        const double* score_in, const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in,
+                        double* score_out, int* len_out, long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det,
+                        int* parent, int* fresh, int S, int A, const int* arc_off, const int* arc_sym, const int* arc_next, const float* arc_w,
+                        const int* fail, const float* fail_w, const int* state_in, const double* bias_in, int* state_out, double* bias_out,
+                        void* ws, const double* fuse_in, double* fuse_out, double sym_bonus, const void* ext_0, int ext_0_dtype, long ext_0_ld,
+                        double ext_0_w, int ext_0_norm, const void* ext_1, int ext_1_dtype, long ext_1_ld, double ext_1_w, int ext_1_norm,
+                        void* stream) {
+    return beam_step_fuse(logits, dtype, ld, B, W, V, blank, t, T_len, score_in, len_in, hist_in, frames_in, tok_lp_in, score_out, len_out,
+                          hist_out, frames_out, tok_lp_out, ld_hist, ld_det, parent, fresh, S, A, arc_off, arc_sym, arc_next, arc_w, fail, fail_w,
+                          state_in, bias_in, state_out, bias_out, ws, fuse_in, fuse_out, sym_bonus, ext_0, ext_0_dtype, ext_0_ld, ext_0_w,
+                          ext_0_norm, ext_1, ext_1_dtype, ext_1_ld, ext_1_w, ext_1_norm, static_cast<hipStream_t>(stream));
+}
 
 // ------------------------------------------------------------------ embedding (tt/decoder.py:26,39)
 int ttmi_embed_fwd(const long* tokens, const float* W, long n, int d, int V, float* out, void* stream) {

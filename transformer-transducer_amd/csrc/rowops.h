@@ -125,6 +125,16 @@ int beam_step_ctx(const void* logits, int dtype, long ld, int B, int W, int V, i
                   long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det, int* parent, int* fresh, int S, int A,
                   const int* arc_off, const int* arc_sym, const int* arc_next, const float* arc_w, const int* fail, const float* fail_w,
                   const int* state_in, const double* bias_in, int* state_out, double* bias_out, void* ws, hipStream_t st);
+// ... and with dense external scores beside the automaton: up to two [B, W, V] sources (a language model's rows, the internal LM's rows), a
+// bonus per symbol and an accumulated external score per slot (ttmi.h: ttmi_beam_step_fuse); ws holds beam_fuse_ws_bytes(B, W, V) bytes
+size_t beam_fuse_ws_bytes(int B, int W, int V);
+int beam_step_fuse(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len, const double* score_in,
+                   const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in, double* score_out, int* len_out,
+                   long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det, int* parent, int* fresh, int S, int A,
+                   const int* arc_off, const int* arc_sym, const int* arc_next, const float* arc_w, const int* fail, const float* fail_w,
+                   const int* state_in, const double* bias_in, int* state_out, double* bias_out, void* ws, const double* fuse_in,
+                   double* fuse_out, double sym_bonus, const void* ext_0, int ext_0_dtype, long ext_0_ld, double ext_0_w, int ext_0_norm,
+                   const void* ext_1, int ext_1_dtype, long ext_1_ld, double ext_1_w, int ext_1_norm, hipStream_t st);
 // batched transpose to bf16: for z = z1*nz2+z2, dst[z][c][r] = src[z1*s1 + z2*s2 + r*ld + c] (r < R, c < C), dst pitch ldd >= R with
 // zero fill in [R, ldd), dst slab = C*ldd.  src_dtype 0 = f32, 1 = bf16.  Produces the K-major operands of the position products.
 int transpose_bf16_batched(const void* src, int src_dtype, long ld, int nz1, int nz2, long s1, long s2, int R, int C, bf16_t* dst,

@@ -1646,12 +1646,26 @@ __global__ void greedy_advance_lp_kernel(unsigned long long* __restrict__ key, i
 //   3. / 4. the blank candidate's key is its finished (merged) score + bias_i; ranks are counted on the keys;
 //   5. lane 0 of the new slot's wave takes step(state_i, k) once more for the winner, by binary search: the same sums in the same order as the
 //      workspace row's, so bias_out is the bias its key was formed with.
+//
+// beam_step_kernel<TL, 2> is ttmi_beam_step_fuse: the biased walk with an accumulated external score per slot and up to two dense [B, W, V]
+// sources (a language model's rows, the internal LM's rows).  What differs from the biased walk:
+//   2. after the main row's log-sum-exp the row's wave takes the log-sum-exp of each source that asks for one (the same single f32 pass),
+//      and the fill of finished biases writes (bias_w + delta) + (fuse_w + e(w, v)) instead, NaN where e is not finite: the sources are
+//      read beside the default's store (and again for the few symbols with an arc), no pass is added, and without a source nothing is
+//      read at all; the candidate passes are the biased walk's, untouched;
+//   3. / 4. the blank candidate's key is its score + (bias_i + fuse_i);
+//   5. lane 0 of the new slot's wave forms e(i, k) once more for the winner (beam_fuse_e: the same roundings as the row's).
 constexpr int BEAM_MAX_W = 32;
 struct BeamCtxArgs {
     int S, A;
     const int *arc_off, *arc_sym, *arc_next; const float* arc_w; const int* fail; const float* fail_w;
     const int* state_in; const double* bias_in; int* state_out; double* bias_out;
     double* ws;                                              // [B, W, V]: a row of finished biases per live slot, rewritten every frame
+};
+struct BeamFuseArgs {                                        // ttmi_beam_step_fuse: dense external scores, a row per slot and source
+    const void* ext[2]; int bf16[2]; long ld[2]; double w[2]; int norm[2];
+    double sym_bonus;
+    const double* fuse_in; double* fuse_out;
 };
 struct BeamStepArgs {
     const void* logits; long ld; int W, V, blank;
@@ -1660,7 +1674,8 @@ struct BeamStepArgs {
     double* score_out; int* len_out; long* hist_out; int* frames_out; float* tok_lp_out;
     long ld_hist, ld_det;
     int *parent, *fresh;
-    BeamCtxArgs x;                                           // read by the biased instantiation only
+    BeamCtxArgs x;                                           // read by the biased instantiations only
+    BeamFuseArgs f;                                          // read by the fused instantiation only
 };
 __device__ __forceinline__ double beam_key(double s) { return s > -INFINITY ? s : -INFINITY; }      // NaN ranks as -inf
 // ---- contextual biasing (ttmi_beam_step_ctx; the automaton's contract and step(s, k) are ttmi.h's).  No index is followed outside the tables,
@@ -1698,17 +1713,67 @@ __device__ __forceinline__ void beam_ctx_drain() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
+// ---- dense external scores (ttmi_beam_step_fuse; the rule: ttmi.h)
+__device__ __forceinline__ float beam_ext_load(const void* p, int bf16, long i) {
+    return bf16 ? bf16_to_f32(static_cast<const bf16_t*>(p)[i]) : static_cast<const float*>(p)[i];
+}
+// a source row's log-sum-exp by its slot's wave, in the single f32 pass the main row's takes; `skip`: an entry left out (-1: none)
+__device__ float beam_ext_lse(const void* p, int bf16, long off, int V, int skip, int lane) {
+    float m = -INFINITY, s = 0.f;
+    for (int v = lane; v < V; v += 64) {
+        const float x = beam_ext_load(p, bf16, off + v);
+        if (x != -INFINITY && v != skip) {
+            const float e = __expf(-fabsf(x - m));
+            if (x > m) { s = s * e + 1.f; m = x; }
+            else s += e;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+        const float nm = fmaxf(m, om);
+        s = s * (m == nm ? 1.f : __expf(m - nm)) + os * (om == nm ? 1.f : __expf(om - nm));
+        m = nm;
+    }
+    const float lse = __shfl(m + logf(s), 0, 64);
+    return lse - lse == 0.f ? lse : NAN;
+}
+// e(w, k) = sym_bonus + w_0 * lpx_0 + w_1 * lpx_1 in f64 in that order, absent sources skipped; the products and sums are rounded one by one
+// (no contraction), so the row's fill and the winner's bookkeeping form the same bits
+__device__ __forceinline__ double beam_fuse_e(const BeamFuseArgs& f, long row, int k, float L0, float L1) {
+#pragma clang fp contract(off)
+    double e = f.sym_bonus;
+    if (f.ext[0]) e += f.w[0] * (double)(beam_ext_load(f.ext[0], f.bf16[0], row * f.ld[0] + k) - L0);
+    if (f.ext[1]) e += f.w[1] * (double)(beam_ext_load(f.ext[1], f.bf16[1], row * f.ld[1] + k) - L1);
+    return e;
+}
+// what the fused step adds to a finished bias x of symbol k: fuse_w + e(w, k), or NaN (a key of -inf) where e is not finite.  Without a
+// source e is the bonus for every symbol and `c0` = fuse_w + sym_bonus is added without a load
+struct BeamFuseRow { long row; float L0, L1; double fw, c0; bool dense; };
+__device__ __forceinline__ double beam_fuse_add(const BeamFuseArgs& f, const BeamFuseRow& r, double x, int k) {
+    if (!r.dense) return x + r.c0;
+    const double e = beam_fuse_e(f, r.row, k, r.L0, r.L1);
+    return (e - e == 0.0) ? x + (r.fw + e) : (double)NAN;
+}
 // the row of finished biases bias_i + delta(s0, v), v in [0, V), by the row's own wave: almost every symbol shares the default (the chain's
 // summed fail_w down to the root, plus fail_w[0]); the row is filled with it and then overwritten with the arcs of the chain's states from the
 // root end upwards, so the first arc on the chain wins.  `ch_s` / `ch_acc`: this wave's BEAM_CTX_CHAIN LDS entries.
-__device__ void beam_ctx_fill(const BeamCtxArgs& x, int s0, double bias, double* row, int V, int* ch_s, double* ch_acc, int lane) {
+// FUSE (ttmi_beam_step_fuse): every value written is the finished bias plus the symbol's fuse_w + e(w, v) (beam_fuse_add), in the same
+// passes: the sources are read once beside the default's store, and once more per arc.
+template <bool FUSE>
+__device__ void beam_ctx_fill(const BeamCtxArgs& x, int s0, double bias, double* row, int V, int* ch_s, double* ch_acc, int lane,
+                              const BeamFuseArgs& f, const BeamFuseRow& fr) {
     int s = s0, D = 0;
     double acc = 0.0;
     do {
         if (D < BEAM_CTX_CHAIN) { ch_s[D] = s; ch_acc[D] = acc; }      // (every lane writes the same value)
     } while (beam_ctx_hop(x, s, acc, D++));
     const double dflt = bias + (acc + (double)x.fail_w[0]);
-    for (int v = lane; v < V; v += 64) row[v] = dflt;
+    if (FUSE && fr.dense) { for (int v = lane; v < V; v += 64) row[v] = beam_fuse_add(f, fr, dflt, v); }
+    else {
+        const double d0 = FUSE ? dflt + fr.c0 : dflt;             // (without a source every symbol adds the same fuse_w + sym_bonus)
+        for (int v = lane; v < V; v += 64) row[v] = d0;
+    }
     for (int L = D - 1; L >= 0; --L) {
         beam_ctx_drain();
         const int from = min(L, BEAM_CTX_CHAIN - 1);
@@ -1718,7 +1783,10 @@ __device__ void beam_ctx_fill(const BeamCtxArgs& x, int s0, double bias, double*
         beam_ctx_arcs(x, s, lo, hi);
         for (int q = lo + lane; q < hi; q += 64) {
             const int sym = x.arc_sym[q];
-            if (sym >= 0 && sym < V) row[sym] = bias + (acc + (double)x.arc_w[q]);
+            if (sym >= 0 && sym < V) {
+                if constexpr (FUSE) row[sym] = beam_fuse_add(f, fr, bias + (acc + (double)x.arc_w[q]), sym);
+                else row[sym] = bias + (acc + (double)x.arc_w[q]);
+            }
         }
     }
     beam_ctx_drain();
@@ -1743,8 +1811,10 @@ __device__ __forceinline__ void beam_copy_slot(const BeamStepArgs& a, long base,
     for (int c = lane; c < n_det && c < a.ld_det; c += 64) { fo[c] = fi[c]; lo[c] = li[c]; }
     if (app_det && lane == 0 && n_det < a.ld_det) { fo[n_det] = app_frame; lo[n_det] = app_lp; }
 }
-template <typename TL, bool CTX>
+// MODE 0: ttmi_beam_step; 1: ttmi_beam_step_ctx; 2: ttmi_beam_step_fuse
+template <typename TL, int MODE>
 __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
+    constexpr bool CTX = MODE >= 1, FUSE = MODE == 2;
     constexpr int MW = BEAM_MAX_W, NC = MW * (MW + 1);
     __shared__ double s_score[MW], c_score[NC];
     __shared__ float s_lse[MW], c_lp[NC], s_mlp[MW];
@@ -1753,6 +1823,9 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
     // the biased instantiation ranks by c_key = score + bias; without a context the key IS the score
     __shared__ double c_keys[CTX ? NC : 1], s_bias[CTX ? MW : 1], ch_acc[CTX ? 4 * BEAM_CTX_CHAIN : 1];
     __shared__ int s_state[CTX ? MW : 1], ch_s[CTX ? 4 * BEAM_CTX_CHAIN : 1];
+    // the fused instantiation: the slot's accumulated external score and its sources' normalisers
+    __shared__ double s_fuse[FUSE ? MW : 1];
+    __shared__ float s_L0[FUSE ? MW : 1], s_L1[FUSE ? MW : 1];
     double* const c_key = CTX ? c_keys : c_score;
     const int b = blockIdx.x, W = a.W, V = a.V, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nc = W * (W + 1);
     const long base = (long)b * W;
@@ -1767,6 +1840,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
                 a.parent[base + w] = w;
                 a.fresh[base + w] = 0;
                 if constexpr (CTX) { a.x.state_out[base + w] = a.x.state_in[base + w]; a.x.bias_out[base + w] = a.x.bias_in[base + w]; }
+                if constexpr (FUSE) a.f.fuse_out[base + w] = a.f.fuse_in[base + w];
             }
         }
         return;
@@ -1786,6 +1860,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
             s_state[tid] = live ? beam_ctx_state(a.x, a.x.state_in[base + tid]) : 0;
             s_bias[tid] = live ? a.x.bias_in[base + tid] : 0.0;
         }
+        if constexpr (FUSE) { s_fuse[tid] = live ? a.f.fuse_in[base + tid] : 0.0; s_L0[tid] = 0.f; s_L1[tid] = 0.f; }
     }
     for (int c = tid; c < nc; c += 256) {
         c_score[c] = -INFINITY; c_sym[c] = -1; c_lp[c] = 0.f;
@@ -1832,7 +1907,16 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
         const double* bp = nullptr;                          // the row's finished biases
         if constexpr (CTX) {
             double* row = a.x.ws + (base + w) * V;
-            beam_ctx_fill(a.x, s_state[w], s_bias[w], row, V, ch_s + wave * BEAM_CTX_CHAIN, ch_acc + wave * BEAM_CTX_CHAIN, lane);
+            BeamFuseRow fr{};
+            if constexpr (FUSE) {
+                // a source row is read here, by the wave of a live slot of an unfinished utterance, and nowhere else but for the winners
+                float L0 = 0.f, L1 = 0.f;
+                if (a.f.ext[0] && a.f.norm[0]) L0 = beam_ext_lse(a.f.ext[0], a.f.bf16[0], (base + w) * a.f.ld[0], V, a.f.norm[0] == 2 ? a.blank : -1, lane);
+                if (a.f.ext[1] && a.f.norm[1]) L1 = beam_ext_lse(a.f.ext[1], a.f.bf16[1], (base + w) * a.f.ld[1], V, a.f.norm[1] == 2 ? a.blank : -1, lane);
+                if (lane == 0) { s_L0[w] = L0; s_L1[w] = L1; }
+                fr = BeamFuseRow{base + w, L0, L1, s_fuse[w], s_fuse[w] + a.f.sym_bonus, a.f.ext[0] || a.f.ext[1]};
+            }
+            beam_ctx_fill<FUSE>(a.x, s_state[w], s_bias[w], row, V, ch_s + wave * BEAM_CTX_CHAIN, ch_acc + wave * BEAM_CTX_CHAIN, lane, a.f, fr);
             bp = row;
         }
         double ps = INFINITY;                                // the previous pick: candidates after it in (score desc, symbol asc) remain
@@ -1888,7 +1972,8 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
             }
         }
         c_score[i * (W + 1)] = sc;
-        if constexpr (CTX) c_key[i * (W + 1)] = beam_key(sc + s_bias[i]);
+        if constexpr (FUSE) c_key[i * (W + 1)] = beam_key(sc + (s_bias[i] + s_fuse[i]));
+        else if constexpr (CTX) c_key[i * (W + 1)] = beam_key(sc + s_bias[i]);
         c_sym[i * (W + 1)] = -1 - from_symbol;               // -1: blank; -2: blank with the details of the merged symbol extension
     } else if (tid < W && s_score[tid] > -INFINITY) {
         // this row has no finite log-sum-exp, but a partner's symbol extension still spells this slot's tokens
@@ -1897,7 +1982,8 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
             const TL* pj = static_cast<const TL*>(a.logits) + (base + j) * a.ld;
             const float l = beam_load(pj + s_msym[i]) - s_lse[j];
             c_score[i * (W + 1)] = beam_key(s_score[j] + (double)l);
-            if constexpr (CTX) c_key[i * (W + 1)] = beam_key(c_score[i * (W + 1)] + s_bias[i]);
+            if constexpr (FUSE) c_key[i * (W + 1)] = beam_key(c_score[i * (W + 1)] + (s_bias[i] + s_fuse[i]));
+            else if constexpr (CTX) c_key[i * (W + 1)] = beam_key(c_score[i * (W + 1)] + s_bias[i]);
             c_sym[i * (W + 1)] = -2;
             s_mlp[i] = l;
         }
@@ -1922,6 +2008,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
             if (lane == 0) {
                 a.score_out[base + r] = -INFINITY; a.len_out[base + r] = 0; a.parent[base + r] = r; a.fresh[base + r] = 0;
                 if constexpr (CTX) { a.x.state_out[base + r] = 0; a.x.bias_out[base + r] = 0.0; }
+                if constexpr (FUSE) a.f.fuse_out[base + r] = 0.0;
             }
             continue;
         }
@@ -1941,6 +2028,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(const BeamStepArgs a) {
                 a.x.state_out[base + r] = next;
                 a.x.bias_out[base + r] = sym >= 0 ? s_bias[i] + delta : s_bias[i];
             }
+            if constexpr (FUSE) a.f.fuse_out[base + r] = sym >= 0 ? s_fuse[i] + beam_fuse_e(a.f, base + i, sym, s_L0[i], s_L1[i]) : s_fuse[i];
         }
     }
 }
@@ -1960,9 +2048,9 @@ int beam_step(const void* logits, int dtype, long ld, int B, int W, int V, int b
     TTMI_REQUIRE(score_in != score_out && len_in != len_out && hist_in != hist_out && (n_det == 0 || (frames_in != frames_out && tok_lp_in != tok_lp_out)),
                  "beam_step: the new beam needs buffers of its own");
     BeamStepArgs a{logits, ld, W, V, blank, t, T_len, score_in, len_in, hist_in, frames_in, tok_lp_in, score_out, len_out, hist_out, frames_out,
-                   tok_lp_out, ld_hist, ld_det, parent, fresh, BeamCtxArgs{}};
-    if (dtype == 0) hipLaunchKernelGGL((beam_step_kernel<float, false>), dim3(B), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((beam_step_kernel<bf16_t, false>), dim3(B), dim3(256), 0, st, a);
+                   tok_lp_out, ld_hist, ld_det, parent, fresh, BeamCtxArgs{}, BeamFuseArgs{}};
+    if (dtype == 0) hipLaunchKernelGGL((beam_step_kernel<float, 0>), dim3(B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((beam_step_kernel<bf16_t, 0>), dim3(B), dim3(256), 0, st, a);
     TTMI_LAUNCH_CHECK("beam_step_kernel");
     return TTMI_OK;
 }
@@ -1992,10 +2080,71 @@ int beam_step_ctx(const void* logits, int dtype, long ld, int B, int W, int V, i
                  "beam_step_ctx: the new beam needs buffers of its own");
     BeamStepArgs a{logits, ld, W, V, blank, t, T_len, score_in, len_in, hist_in, frames_in, tok_lp_in, score_out, len_out, hist_out, frames_out,
                    tok_lp_out, ld_hist, ld_det, parent, fresh,
-                   BeamCtxArgs{S, A, arc_off, arc_sym, arc_next, arc_w, fail, fail_w, state_in, bias_in, state_out, bias_out, static_cast<double*>(ws)}};
-    if (dtype == 0) hipLaunchKernelGGL((beam_step_kernel<float, true>), dim3(B), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((beam_step_kernel<bf16_t, true>), dim3(B), dim3(256), 0, st, a);
+                   BeamCtxArgs{S, A, arc_off, arc_sym, arc_next, arc_w, fail, fail_w, state_in, bias_in, state_out, bias_out, static_cast<double*>(ws)},
+                   BeamFuseArgs{}};
+    if (dtype == 0) hipLaunchKernelGGL((beam_step_kernel<float, 1>), dim3(B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((beam_step_kernel<bf16_t, 1>), dim3(B), dim3(256), 0, st, a);
     TTMI_LAUNCH_CHECK("beam_step_ctx_kernel");
+    return TTMI_OK;
+}
+
+size_t beam_fuse_ws_bytes(int B, int W, int V) { return beam_ctx_ws_bytes(B, W, V); }
+
+int beam_step_fuse(const void* logits, int dtype, long ld, int B, int W, int V, int blank, const int* t, const int* T_len, const double* score_in,
+                   const int* len_in, const long* hist_in, const int* frames_in, const float* tok_lp_in, double* score_out, int* len_out,
+                   long* hist_out, int* frames_out, float* tok_lp_out, long ld_hist, long ld_det, int* parent, int* fresh, int S, int A,
+                   const int* arc_off, const int* arc_sym, const int* arc_next, const float* arc_w, const int* fail, const float* fail_w,
+                   const int* state_in, const double* bias_in, int* state_out, double* bias_out, void* ws, const double* fuse_in,
+                   double* fuse_out, double sym_bonus, const void* ext_0, int ext_0_dtype, long ext_0_ld, double ext_0_w, int ext_0_norm,
+                   const void* ext_1, int ext_1_dtype, long ext_1_ld, double ext_1_w, int ext_1_norm, hipStream_t st) {
+    TTMI_REQUIRE(logits && t && T_len && score_in && len_in && hist_in && score_out && len_out && hist_out && parent && fresh,
+                 "beam_step_fuse: null pointer");
+    TTMI_REQUIRE(arc_off && fail && fail_w && state_in && bias_in && state_out && bias_out && ws && fuse_in && fuse_out,
+                 "beam_step_fuse: null pointer");
+    TTMI_REQUIRE(S >= 1 && A >= 0, "beam_step_fuse: an automaton has at least its root and no negative arc count, got S = %d, A = %d", S, A);
+    TTMI_REQUIRE(A == 0 || (arc_sym && arc_next && arc_w), "beam_step_fuse: null pointer (arc tables)");
+    const int n_det = !!frames_in + !!tok_lp_in + !!frames_out + !!tok_lp_out;
+    TTMI_REQUIRE(n_det == 0 || n_det == 4, "beam_step_fuse: frames / tok_lp come as all four arrays or none");
+    TTMI_REQUIRE(dtype == 0 || dtype == 1, "beam_step_fuse: logits are f32 (0) or bf16 (1)");
+    TTMI_REQUIRE(W >= 1 && W <= BEAM_MAX_W, "beam_step_fuse: beam width %d outside [1, %d]", W, BEAM_MAX_W);
+    TTMI_REQUIRE(B > 0 && V >= 2 && ld >= V && blank >= 0 && blank < V && ld_hist >= 2 && (n_det == 0 || ld_det >= 1),
+                 "beam_step_fuse: bad arguments");
+    TTMI_REQUIRE(score_in != score_out && len_in != len_out && hist_in != hist_out && (n_det == 0 || (frames_in != frames_out && tok_lp_in != tok_lp_out)) &&
+                     state_in != state_out && bias_in != bias_out && fuse_in != fuse_out,
+                 "beam_step_fuse: the new beam needs buffers of its own");
+    TTMI_REQUIRE(sym_bonus - sym_bonus == 0.0, "beam_step_fuse: sym_bonus must be finite");
+    const void* const ext[2] = {ext_0, ext_1};
+    const int ext_dtype[2] = {ext_0_dtype, ext_1_dtype}, ext_norm[2] = {ext_0_norm, ext_1_norm};
+    const long ext_ld[2] = {ext_0_ld, ext_1_ld};
+    const double ext_w[2] = {ext_0_w, ext_1_w};
+    const size_t bw = (size_t)B * W;
+    for (int j = 0; j < 2; ++j) {
+        if (!ext[j]) continue;
+        TTMI_REQUIRE(ext_dtype[j] == 0 || ext_dtype[j] == 1, "beam_step_fuse: source %d is f32 (0) or bf16 (1), got dtype %d", j, ext_dtype[j]);
+        TTMI_REQUIRE(ext_norm[j] >= 0 && ext_norm[j] <= 2, "beam_step_fuse: source %d has norm %d outside 0..2", j, ext_norm[j]);
+        TTMI_REQUIRE(ext_w[j] - ext_w[j] == 0.0, "beam_step_fuse: the weight of source %d must be finite", j);
+        TTMI_REQUIRE(ext_ld[j] >= V, "beam_step_fuse: source %d has row pitch %ld < V = %d", j, ext_ld[j], V);
+        // a source the kernel reads while it writes the new beam: it may overlap no output
+        const char* lo = static_cast<const char*>(ext[j]);
+        const char* hi = lo + ((bw - 1) * (size_t)ext_ld[j] + (size_t)V) * (ext_dtype[j] ? 2 : 4);
+        const struct { const void* p; size_t bytes; } outs[] = {
+            {score_out, bw * 8}, {len_out, bw * 4}, {hist_out, bw * (size_t)ld_hist * 8}, {frames_out, bw * (size_t)ld_det * 4},
+            {tok_lp_out, bw * (size_t)ld_det * 4}, {parent, bw * 4}, {fresh, bw * 4}, {state_out, bw * 4}, {bias_out, bw * 8},
+            {fuse_out, bw * 8}, {ws, beam_fuse_ws_bytes(B, W, V)}};
+        for (const auto& o : outs) {
+            const char* q = static_cast<const char*>(o.p);
+            TTMI_REQUIRE(!q || q + o.bytes <= lo || hi <= q, "beam_step_fuse: source %d overlaps an output buffer", j);
+        }
+    }
+    BeamFuseArgs f{{ext_0, ext_1}, {ext_0_dtype, ext_1_dtype}, {ext_0_ld, ext_1_ld}, {ext_0_w, ext_1_w}, {ext_0_norm, ext_1_norm}, sym_bonus,
+                   fuse_in, fuse_out};
+    BeamStepArgs a{logits, ld, W, V, blank, t, T_len, score_in, len_in, hist_in, frames_in, tok_lp_in, score_out, len_out, hist_out, frames_out,
+                   tok_lp_out, ld_hist, ld_det, parent, fresh,
+                   BeamCtxArgs{S, A, arc_off, arc_sym, arc_next, arc_w, fail, fail_w, state_in, bias_in, state_out, bias_out, static_cast<double*>(ws)},
+                   f};
+    if (dtype == 0) hipLaunchKernelGGL((beam_step_kernel<float, 2>), dim3(B), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((beam_step_kernel<bf16_t, 2>), dim3(B), dim3(256), 0, st, a);
+    TTMI_LAUNCH_CHECK("beam_step_fuse_kernel");
     return TTMI_OK;
 }
 

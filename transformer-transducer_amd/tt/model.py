@@ -1348,7 +1348,8 @@ class Transducer(nn.Module):
         return [self.decode(enc_states[b], inputs_length[b]) for b in range(inputs.size(0))]
 
     @torch.no_grad()
-    def beam_decode_batch(self, enc_states, lengths, beam_width=4, nbest=None, context=None, return_bias=False):
+    def beam_decode_batch(self, enc_states, lengths, beam_width=4, nbest=None, context=None, return_bias=False, lm=None, lm_weight=0.0,
+                          ilm_weight=0.0, length_bonus=0.0, return_lm=False):
         """Frame-synchronous beam search of EVERY utterance of a batch at once -> per utterance a list of at most `nbest` (default: beam_width)
         DecodeResult, best first.  The probability model is the greedy decoder's (`decode_batch`): each of an utterance's T_b frames takes one
         decision, blank or one symbol, against the label state of the tokens so far, and the emitting frame is consumed.  Unlike `beam_search`
@@ -1366,6 +1367,15 @@ class Transducer(nn.Module):
         begun and not finished keeps nothing) and the list is ordered by score + final_bias, descending, the slot ascending on ties, then cut
         to `nbest`.  `score` stays the model's log-probability (comparable with greedy scores, usable by mwer_loss).  return_bias=True ->
         (results, biases): biases[b][n] = the final bias of results[b][n], 0.0 without a context.  context=None runs ttmi_beam_step as before.
+        lm = a language model scorer (ttmi.lm has the protocol and TransformerLM), fused into the search: with lm, ilm_weight or length_bonus
+        given, every frame runs ttmi_beam_step_fuse (include/ttmi.h has the rule) on two more [B, W, V] row tables kept like the label
+        states (gathered by `parent`, recomputed for `fresh` slots only, the LM called once per distinct history length): source 0 = the
+        LM's rows at lm_weight, source 1 = the internal LM's rows self.joint(zero encoder state, label state) at -ilm_weight, renormalised
+        without the blank (internal-LM subtraction), and length_bonus per emitted symbol.  The selection of every frame is by
+        score + bias + fuse; after the last frame lm_total = fuse + lm_weight * log P_lm(eos | tokens) where lm.eos is not None, and the
+        list is ordered by score + final_bias + lm_total.  `score` stays the model's log-probability.  return_lm=True appends the
+        lm_totals to the return, as return_bias does the biases.  Hotwords and an n-gram automaton at once need a product automaton: one
+        context= per call.  Without lm, ilm_weight and length_bonus the calls are the ones above, launch for launch.
         Not built: a cache of label states for sequences seen on earlier frames, a captured graph of the loop, a streaming variant."""
         if not enc_states.is_cuda:
             raise ValueError("beam_decode_batch: enc_states must live on the GPU (the MI355X build has no CPU path)")
@@ -1373,6 +1383,16 @@ class Transducer(nn.Module):
         nbest = W if nbest is None else int(nbest)
         if not 1 <= W <= 32 or nbest < 1:
             raise ValueError("beam_decode_batch: beam_width must be in [1, 32] and nbest >= 1, got %r and %r" % (beam_width, nbest))
+        for name, v in (("lm_weight", lm_weight), ("ilm_weight", ilm_weight), ("length_bonus", length_bonus)):
+            if not math.isfinite(float(v)) or (name != "length_bonus" and float(v) < 0.0):
+                raise ValueError("beam_decode_batch: %s must be finite%s, got %r" % (name, "" if name == "length_bonus" else " and >= 0", v))
+        lm_weight, ilm_weight, length_bonus = float(lm_weight), float(ilm_weight), float(length_bonus)
+        fused = lm is not None or ilm_weight != 0.0 or length_bonus != 0.0
+        if lm is not None:
+            if lm.norm not in ops.BEAM_FUSE_NORMS:
+                raise ValueError("beam_decode_batch: lm.norm must be one of %s, got %r" % (sorted(ops.BEAM_FUSE_NORMS), lm.norm))
+            if isinstance(lm, nn.Module) and any(not p.is_cuda for p in lm.parameters()):
+                raise ValueError("beam_decode_batch: the language model must live on the GPU (the MI355X build has no CPU path)")
         dev = enc_states.device
         B, T = enc_states.shape[0], enc_states.shape[1]
         lens = [T] * B if lengths is None else [min(int(v), T) for v in torch.as_tensor(lengths).tolist()]
@@ -1396,65 +1416,133 @@ class Transducer(nn.Module):
             for bm in (cur, nxt):
                 bm["ctx"] = (torch.zeros(B, W, dtype=torch.int32, device=dev), torch.zeros(B, W, dtype=torch.float64, device=dev))
             ctx_ws = ops.beam_ctx_workspace(B, W, self.config.vocab_size, dev)
+            if context.start:                                        # (an n-gram automaton starts in its <s> context)
+                cur["ctx"][0][:, 0] = int(context.start)
         parent = torch.zeros(B, W, dtype=torch.int32, device=dev)
         start = self.decoder(torch.zeros(1, 1, dtype=torch.long, device=dev))[:, -1, :]
         states = start[None].expand(B, W, -1).contiguous()           # [B, W, d]; what an empty slot holds is never read by the kernel
         d = states.shape[-1]
+        lm_rows = ilm_rows = None
+        need_eos = lm is not None and lm.eos is not None
+        if fused:
+            V = self.config.vocab_size
+            if context is None:                                      # the trivial automaton: the root alone, every weight 0
+                tables = tuple(torch.zeros(n, dtype=dt, device=dev) for n, dt in ((2, torch.int32), (0, torch.int32), (0, torch.int32),
+                                                                                   (0, torch.float32), (1, torch.int32), (1, torch.float32)))
+                for bm in (cur, nxt):
+                    bm["ctx"] = (torch.zeros(B, W, dtype=torch.int32, device=dev), torch.zeros(B, W, dtype=torch.float64, device=dev))
+            else:
+                tables = context.tables
+            for bm in (cur, nxt):
+                bm["fuse"] = torch.zeros(B, W, dtype=torch.float64, device=dev)
+            fuse_ws = ops.beam_fuse_workspace(B, W, V, dev)
+            zero_enc = torch.zeros(1, 1, enc_states.shape[-1], dtype=enc_states.dtype, device=dev)
+
+            def lm_scores(hist):
+                rows = lm.next_logits(hist)
+                if not rows.is_cuda or rows.dim() != 2 or rows.shape[1] != V or rows.dtype not in (torch.float32, torch.bfloat16):
+                    raise ValueError("beam_decode_batch: lm.next_logits must return [N, %d] f32 or bf16 rows on the GPU" % V)
+                return rows
+
+            def ilm_scores(st):
+                """the joint without an encoder: the label encoder's own prior (internal LM), [N, d] -> [N, V]"""
+                return self.joint(zero_enc, st[None].contiguous())[0, 0]
+            if lm is not None:
+                lm_rows = lm_scores(torch.zeros(1, 1, dtype=torch.long, device=dev))[None].expand(B, W, -1).contiguous()
+            if ilm_weight != 0.0:
+                ilm_rows = ilm_scores(start)[None].expand(B, W, -1).contiguous()
         for f in range(T_max):
             logits = self.joint(enc_states[:, f:f + 1].contiguous(), states)                      # [B, 1, W, V]
-            if context is None:
+            if fused:
+                ops.beam_step_fuse(logits[:, 0], t, T_len, arrays(cur), arrays(nxt), parent, nxt["meta"][1], tables, cur["ctx"], nxt["ctx"],
+                                   fuse_ws, cur["fuse"], nxt["fuse"],
+                                   sources=(None if lm is None else (lm_rows, lm_weight, ops.BEAM_FUSE_NORMS[lm.norm]),
+                                            None if ilm_rows is None else (ilm_rows, -ilm_weight, 2)), sym_bonus=length_bonus, blank=0)
+            elif context is None:
                 ops.beam_step(logits[:, 0], t, T_len, arrays(cur), arrays(nxt), parent, nxt["meta"][1], blank=0)
             else:
                 ops.beam_step_ctx(logits[:, 0], t, T_len, arrays(cur), arrays(nxt), parent, nxt["meta"][1], context.tables, cur["ctx"],
                                   nxt["ctx"], ctx_ws, blank=0)
             t += 1
             cur, nxt = nxt, cur
-            if f == T_max - 1:
+            if f == T_max - 1 and not need_eos:
                 break
             n_tok, fresh = cur["meta"].cpu().tolist()                                             # the frame's one host round trip
-            states = states.gather(1, parent.long()[:, :, None].expand(-1, -1, d))                # a slot that keeps its tokens keeps its label state
-            by_len = {}
+            gather = parent.long()[:, :, None]
+            if f < T_max - 1:
+                states = states.gather(1, gather.expand(-1, -1, d))                               # a slot that keeps its tokens keeps its label state
+                if ilm_rows is not None:
+                    ilm_rows = ilm_rows.gather(1, gather.expand(-1, -1, V))
+            if lm_rows is not None:
+                lm_rows = lm_rows.gather(1, gather.expand(-1, -1, V))
+            by_len, lm_only = {}, {}
             for b in range(B):
-                if f + 1 >= lens[b] or not any(fresh[b]):                                         # (an utterance without frames left reads no label state again)
+                # an utterance without frames left reads no label state again; its closing frame's new sequences still need the LM's eos term
+                which = by_len if f + 1 < lens[b] else lm_only if (need_eos and f + 1 == lens[b]) else None
+                if which is None or not any(fresh[b]):
                     continue
                 for w in range(W):
                     if fresh[b][w]:
-                        by_len.setdefault(n_tok[b][w], []).append(b * W + w)
-            for n, rows in sorted(by_len.items()):
-                rows = torch.tensor(rows, dtype=torch.long, device=dev)
-                hist = cur["hist"].view(B * W, ld_hist)[rows, :n + 1]
-                states.view(B * W, d).index_copy_(0, rows, self.decoder(hist.contiguous())[:, -1, :])
+                        which.setdefault(n_tok[b][w], []).append(b * W + w)
+            for n in sorted(set(by_len) | set(lm_only)):
+                if n in by_len:
+                    rows = torch.tensor(by_len[n], dtype=torch.long, device=dev)
+                    hist = cur["hist"].view(B * W, ld_hist)[rows, :n + 1].contiguous()
+                    st = self.decoder(hist)[:, -1, :]
+                    states.view(B * W, d).index_copy_(0, rows, st)
+                    if ilm_rows is not None:
+                        ilm_rows.view(B * W, V).index_copy_(0, rows, ilm_scores(st).to(ilm_rows.dtype))
+                if lm_rows is not None:
+                    if n in lm_only:                                                              # one LM call per history length all the same
+                        rows = torch.tensor(by_len.get(n, []) + lm_only[n], dtype=torch.long, device=dev)
+                        hist = cur["hist"].view(B * W, ld_hist)[rows, :n + 1].contiguous()
+                    lm_rows.view(B * W, V).index_copy_(0, rows, lm_scores(hist).to(lm_rows.dtype))
         # ONE transfer, as f64 (exact for token ids, counts, frames and f32 log-probabilities): score | len | tokens | frames | logprobs
         packed = torch.cat([cur["score"][:, :, None], cur["meta"][0].double()[:, :, None], cur["hist"][:, :, 1:].double(), cur["frames"].double(),
                             cur["tok_lp"].double()] +
-                           ([] if context is None else [(cur["ctx"][1] + context.final_w[cur["ctx"][0].long()].double())[:, :, None]]), dim=2).cpu()
-        out, biases = [], []
+                           ([] if context is None else [(cur["ctx"][1] + context.final_w[cur["ctx"][0].long()].double())[:, :, None]]), dim=2)
+        if fused:
+            from ttmi.lm import eos_logprob
+            lm_total = cur["fuse"] + lm_weight * eos_logprob(lm_rows, lm.norm, lm.eos) if need_eos else cur["fuse"]
+            packed = torch.cat([packed, lm_total[:, :, None]], dim=2)
+        packed = packed.cpu()
+        bias_col = -1 - int(fused)
+        out, biases, lms = [], [], []
         for b in range(B):
-            res, bias = [], []
+            res, bias, lmt = [], [], []
             for w in range(W):
                 score, c = float(packed[b, w, 0]), int(packed[b, w, 1])
                 if not score > -math.inf:                            # an empty slot
                     continue
                 tok, frm, lpr = (packed[b, w, 2 + i * ld_det:2 + i * ld_det + c].tolist() for i in range(3))
                 res.append(DecodeResult([int(v) for v in tok], [int(v) for v in frm], lpr, score))
-                bias.append(0.0 if context is None else float(packed[b, w, -1]))
-            if context is not None:                                  # the slots are in key order with the running bias; the final bias reorders
+                bias.append(0.0 if context is None else float(packed[b, w, bias_col]))
+                lmt.append(float(packed[b, w, -1]) if fused else 0.0)
+            if fused:                                                # ... and so does the LM's closing term
+                order = sorted(range(len(res)), key=lambda n: (-(res[n].score + bias[n] + lmt[n]), n))
+                res, bias, lmt = [res[n] for n in order], [bias[n] for n in order], [lmt[n] for n in order]
+            elif context is not None:                                # the slots are in key order with the running bias; the final bias reorders
                 order = sorted(range(len(res)), key=lambda n: (-(res[n].score + bias[n]), n))
                 res, bias = [res[n] for n in order], [bias[n] for n in order]
             if not res or not math.isfinite(res[0].score):
                 raise RuntimeError("beam search: utterance %d has no hypothesis with a finite score (NaN logits?)" % b)
             out.append(res[:nbest])
             biases.append(bias[:nbest])
-        return (out, biases) if return_bias else out
+            lms.append(lmt[:nbest])
+        ret = (out,) + ((biases,) if return_bias else ()) + ((lms,) if return_lm else ())
+        return ret if len(ret) > 1 else out
 
     @torch.no_grad()
-    def recognize_nbest(self, inputs, inputs_length=None, audio_mask=None, beam_width=4, nbest=None, context=None, return_bias=False):
+    def recognize_nbest(self, inputs, inputs_length=None, audio_mask=None, beam_width=4, nbest=None, context=None, return_bias=False, lm=None,
+                        lm_weight=0.0, ilm_weight=0.0, length_bonus=0.0, return_lm=False):
         """N-best recognition of a batch: the encoder, then `beam_decode_batch` -> per utterance a list of at most `nbest` (default:
-        beam_width) DecodeResult, best first, with merged, comparable scores; `context` / `return_bias`: contextual biasing, see there"""
+        beam_width) DecodeResult, best first, with merged, comparable scores; `context` / `return_bias`: contextual biasing, `lm` /
+        `lm_weight` / `ilm_weight` / `length_bonus` / `return_lm`: language-model fusion, see there"""
         if not inputs.is_cuda:
             raise ValueError("recognize_nbest: inputs must live on the GPU (the MI355X build has no CPU path)")
         enc_states = self.encoder(inputs, audio_mask)
-        return self.beam_decode_batch(enc_states, inputs_length, beam_width=beam_width, nbest=nbest, context=context, return_bias=return_bias)
+        return self.beam_decode_batch(enc_states, inputs_length, beam_width=beam_width, nbest=nbest, context=context, return_bias=return_bias,
+                                      lm=lm, lm_weight=lm_weight, ilm_weight=ilm_weight, length_bonus=length_bonus, return_lm=return_lm)
 
     @torch.no_grad()
     def beam_search(self, enc_state, lengths, beam_width=5, block=64):

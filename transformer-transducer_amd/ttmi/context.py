@@ -5,6 +5,7 @@ ContextGraph(phrases, boost)     the hotword compiler: phrase trie + Aho-Corasic
 ContextGraph.from_tables(...)    any automaton that meets the contract
 .validate(V)                     checks the CPU copy of the tables before any launch
 .to(device)                      uploads the tables once; .tables / .final_w are then device tensors
+.start                           the state slot 0 starts in: 0, the root (ttmi.lm.NGramLM.from_arpa sets the <s> context)
 
 What the compiled weights mean.  A finished phrase p is worth boost_p * len(p), counted once per occurrence in the token sequence, overlapping
 occurrences included.  A phrase that has been begun is paid in advance, boost * (tokens matched so far), so that its first token already rises
@@ -98,6 +99,7 @@ class ContextGraph:
         self.tables, self.final_w = self._cpu, self._cpu_final
         self.S, self.A = int(self._cpu[4].shape[0]), int(self._cpu[1].shape[0])
         self._device = {}
+        self.start = 0                                               # the state the search starts in: the root for everything built here
 
     def cpu_tables(self):
         """(arc_off, arc_sym, arc_next, arc_w, fail, fail_w, final_w) as CPU tensors"""

@@ -1189,6 +1189,75 @@ def beam_step_ctx(logits, t, T_len, beam_in, beam_out, parent, fresh, tables, ct
                                    _p(ctx_out[0]), _p(ctx_out[1]), _p(ws), _stream()), "ttmi_beam_step_ctx")
 
 
+BEAM_FUSE_NORMS = {"logprob": 0, "softmax": 1, "softmax_no_blank": 2}
+
+
+def beam_fuse_workspace(B, W, V, device):
+    """the workspace of beam_step_fuse for [B, W, V] logits (ttmi_beam_fuse_ws_bytes): allocate once per decoding run, nothing is kept in it"""
+    f = lib().ttmi_beam_fuse_ws_bytes
+    f.restype = ctypes.c_size_t
+    return torch.empty(f(c_int(B), c_int(W), c_int(V)), dtype=torch.uint8, device=device)
+
+
+def beam_step_fuse(logits, t, T_len, beam_in, beam_out, parent, fresh, tables, ctx_in, ctx_out, ws, fuse_in, fuse_out, sources=(),
+                   sym_bonus=0.0, blank=0):
+    """beam_step_ctx with dense external scores (include/ttmi.h: ttmi_beam_step_fuse, the rule is written there): language-model fusion and
+    internal-LM subtraction.  The arguments of beam_step_ctx (tables: a search without hotwords passes the trivial automaton, S = 1, A = 0),
+    ws = beam_fuse_workspace(B, W, V, device), then fuse_in / fuse_out f64 [B, W], swapped with the beam, and `sources`: at most two
+    entries, source 0 and source 1, each None (absent) or (rows, weight, norm) with rows [B, W, V] f32 / bf16 (row (b, w) scores the hypothesis of slot w; row pitch = stride(-2)), weight a float
+    and norm 0 / 1 / 2 (BEAM_FUSE_NORMS: the row holds log-probabilities / logits to normalise / logits to normalise without the blank).
+    Device only, no synchronisation."""
+    B, W, V = logits.shape
+    (s0, n0, h0, f0, l0), (s1, n1, h1, f1, l1) = beam_in, beam_out
+    arc_off, arc_sym, arc_next, arc_w, fail, fail_w = tables
+    sources = list(sources)
+    if len(sources) > 2:
+        raise ValueError("beam_step_fuse: at most two sources, got %d" % len(sources))
+    _need_cuda(logits, t, T_len, s0, n0, h0, f0, l0, s1, n1, h1, f1, l1, parent, fresh, *tables, *ctx_in, *ctx_out, ws, fuse_in, fuse_out,
+               *[src[0] for src in sources if src is not None])
+    if logits.stride(-1) != 1 or (B > 1 and logits.stride(0) != W * logits.stride(1)):
+        raise ValueError("beam_step_fuse: logits rows must be evenly pitched ([B, W, V] with stride(0) = W * stride(1))")
+    for x in (t, T_len):
+        assert x.dtype is torch.int32 and x.is_contiguous() and x.shape[0] == B
+    for s, n, h, f, l in (beam_in, beam_out):
+        assert s.dtype is torch.float64 and s.is_contiguous() and tuple(s.shape) == (B, W)
+        assert n.dtype is torch.int32 and n.is_contiguous() and tuple(n.shape) == (B, W)
+        assert h.dtype is torch.long and h.is_contiguous() and tuple(h.shape[:2]) == (B, W) and h.shape == h0.shape
+        assert (f is None) == (l is None) == (f0 is None)
+        if f is not None:
+            assert f.dtype is torch.int32 and l.dtype is torch.float32 and f.is_contiguous() and l.is_contiguous()
+            assert tuple(f.shape[:2]) == (B, W) and f.shape == l.shape == f0.shape
+    for x in (parent, fresh):
+        assert x.dtype is torch.int32 and x.is_contiguous() and tuple(x.shape) == (B, W)
+    S, A = fail.shape[0], arc_sym.shape[0]
+    for x, dt, n in ((arc_off, torch.int32, S + 1), (arc_sym, torch.int32, A), (arc_next, torch.int32, A), (arc_w, torch.float32, A),
+                     (fail, torch.int32, S), (fail_w, torch.float32, S)):
+        assert x.dtype is dt and x.is_contiguous() and tuple(x.shape) == (n,)
+    for state, bias in (ctx_in, ctx_out):
+        assert state.dtype is torch.int32 and state.is_contiguous() and tuple(state.shape) == (B, W)
+        assert bias.dtype is torch.float64 and bias.is_contiguous() and tuple(bias.shape) == (B, W)
+    for x in (fuse_in, fuse_out):
+        assert x.dtype is torch.float64 and x.is_contiguous() and tuple(x.shape) == (B, W)
+    f = lib().ttmi_beam_fuse_ws_bytes
+    f.restype = ctypes.c_size_t
+    assert ws.is_contiguous() and ws.numel() * ws.element_size() >= f(c_int(B), c_int(W), c_int(V)) and ws.data_ptr() % 8 == 0
+    ext = []
+    for src in sources + [None] * (2 - len(sources)):
+        if src is None:
+            ext += [c_void_p(0), c_int(0), c_long(0), ctypes.c_double(0.0), c_int(0)]
+            continue
+        rows, weight, norm = src
+        if rows.dtype not in _DT or tuple(rows.shape) != (B, W, V) or rows.stride(-1) != 1 or (B > 1 and rows.stride(0) != W * rows.stride(1)):
+            raise ValueError("beam_step_fuse: a source is [B, W, V] f32 / bf16 rows, evenly pitched (stride(0) = W * stride(1)), last stride 1")
+        ext += [_p(rows), c_int(_DT[rows.dtype]), c_long(rows.stride(-2)), ctypes.c_double(float(weight)), c_int(int(norm))]
+    check(lib().ttmi_beam_step_fuse(_p(logits), c_int(_DT[logits.dtype]), c_long(logits.stride(-2)), c_int(B), c_int(W), c_int(V), c_int(blank),
+                                    _p(t), _p(T_len), _p(s0), _p(n0), _p(h0), _p(f0), _p(l0), _p(s1), _p(n1), _p(h1), _p(f1), _p(l1),
+                                    c_long(h0.shape[2]), c_long(f0.shape[2] if f0 is not None else 0), _p(parent), _p(fresh), c_int(S), c_int(A),
+                                    _p(arc_off), _p(arc_sym), _p(arc_next), _p(arc_w), _p(fail), _p(fail_w), _p(ctx_in[0]), _p(ctx_in[1]),
+                                    _p(ctx_out[0]), _p(ctx_out[1]), _p(ws), _p(fuse_in), _p(fuse_out), ctypes.c_double(float(sym_bonus)), *ext,
+                                    _stream()), "ttmi_beam_step_fuse")
+
+
 # ----------------------------------------------------------------------------- error counting (ttmi.metrics)
 def edit_distance(hyp, hyp_len, ref, ref_len, ref_index=None):
     """hyp i32 [P, Lh] / ref i32 [R, Lr] (last stride 1, any row pitch), hyp_len i32 [P], ref_len i32 [R], ref_index i32 [P] or None
