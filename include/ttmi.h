@@ -232,6 +232,44 @@ int ttmi_ctc_loss_bwd(const float* logits, long ldv, const int* labels, const in
 int ttmi_ctc_greedy(const float* logits, long ld, const int* act_lens, int B, int T, int V, int blank,
                     int* tokens /* [B, T] */, int* count /* [B] */, void* stream);
 
+/* ---- forced alignment and emission statistics on the CTC lattice (no reference counterpart) ---------------------------------------------
+ * The twins of ttmi_rnnt_align / _emit_stats and ttmi_mono_align / _emit_stats on the lattice of the auxiliary head.  Both READ the workspace
+ * a finished ttmi_ctc_loss_fwd left on the same (B, T, U) - lp, alpha, beta, ll - and write nothing into it: a ttmi_ctc_loss_bwd issued after
+ * them gives the same bits as one issued straight after the forward.  Lengths and labels are clamped as in ttmi_ctc_loss_fwd, the extended
+ * sequence l' (S = 2 U_b + 1 states) is built literally in the same way, and the skip rule is the loss's: the s-2 move only when
+ * l'_s != blank and l'_s != l'_{s-2} - hence labels, label_lens, V and blank beside the workspace.
+ * ttmi_ctc_align: the best path, frontier in fp64 like alpha; lp is the workspace's f32 table.
+ *     v(0,0) = lp(0,0), v(0,1) = lp(0,1), every other state of frame 0 dead
+ *     v(t,s) = lp(t,s) + max(v(t-1,s), v(t-1,s-1), v(t-1,s-2))            the s-2 term under the skip rule only
+ * TIE RULE: predecessors are tried in the order s, s-1, s-2; a later one replaces an earlier one only when STRICTLY greater.  The path ends
+ * in S-1 unless v(T_b-1, S-2) is strictly greater (U_b = 0: one state).  score f32 [B]: the log-probability of that path.  path i32 [B, T]:
+ * the state index s at frame t < T_b, -1 for t >= T_b.  spans i32 [B, U, 2]: (first, last) frame on which the path sits in state 2u+1, so
+ * first <= last < first of u+1; (-1, -1) for u >= U_b.  An utterance with no feasible alignment - best final value below the threshold that
+ * makes the loss +inf - has score = -inf and every path and spans entry -1, never NaN; its neighbours are unaffected.  Whatever the
+ * workspace holds, NaN included, the backtrace follows no index outside its arrays (s only decreases and is clamped at 0).
+ * Decisions: one bit per blank state, two per label state (1.5 bits per cell), three 8-byte words per frame and 64 label positions; kept in
+ * LDS when an utterance's T * ceil((U + 1) / 64) * 3 words fit 128 KB, otherwise in align_workspace (ttmi_ctc_align_workspace_bytes(B, T, U)
+ * bytes, 8-byte aligned, always required, contents undefined afterwards).  ttmi_set_option(23, bits) is honoured as by ttmi_rnnt_align -
+ * measurements / tests only: 1 = decision words in align_workspace whatever the shape, 2 = no backtrace (path entries t < T_b and spans
+ * entries u < U_b are then not written).
+ * ttmi_ctc_emit_stats: with s = 2u+1, g(t,s) = exp(alpha(t,s) + beta(t,s) - lp(t,s) - ll) is the posterior probability that frame t sits in
+ * label u's state, and e(t,u) the posterior probability that label u's run STARTS at frame t:
+ *     e(t,u) = exp(logsumexp(alpha(t-1,s-1), alpha(t-1,s-2) [skip rule]) + beta(t,s) - ll)   for t > 0  (beta includes the emission at t)
+ *     e(0,0) = g(0,1),  e(0,u>0) = 0
+ * mass f32 [B, U] = sum_t e(t,u) (1 for a healthy lattice: every alignment enters every label state exactly once), expected f32 [B, U] =
+ * sum_t t e(t,u), the expected onset frame, duration f32 [B, U] = sum_t g(t, 2u+1), the expected number of frames the label occupies.
+ * The sums are fp64, in frame order, by one owner; no floating-point atomics: two runs give the same bits.  Entries u >= U_b, and every
+ * entry of an utterance with no feasible alignment: mass 0, expected -1, duration 0.
+ * Neither call allocates, synchronises with the host or issues a memset node; both may be captured in a HIP graph.  rc < 0 with a
+ * ttmi_last_error text, before any launch, on a null pointer (labels / spans / the statistics may be null when U = 0), B or T < 1, U < 0 or
+ * U > 1023, V < 2, blank outside [0, V), a workspace that is not 16-byte aligned or an align_workspace that is not 8-byte aligned. */
+size_t ttmi_ctc_align_workspace_bytes(int B, int T, int U);
+int ttmi_ctc_align(const void* workspace /* filled by ttmi_ctc_loss_fwd on the same (B,T,U) */, const int* labels, const int* act_lens,
+                   const int* label_lens, int B, int T, int U, int V, int blank, void* align_workspace,
+                   int* path /* [B,T] */, int* spans /* [B,U,2] */, float* score /* [B] */, void* stream);
+int ttmi_ctc_emit_stats(const void* workspace, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U, int V,
+                        int blank, float* expected, float* mass, float* duration /* each [B,U] */, void* stream);
+
 /* ---- monotonic RNN-T loss (Tripathi et al. 2019, "Monotonic RNN-T"; no reference counterpart) --------------------------------------------
  * The forward-backward over the lattice the decoders of this library walk (ttmi_greedy_*, ttmi_beam_step[_ctx]): every frame makes exactly
  * ONE decision, blank or one label, and the emitting frame is consumed - where the standard lattice above lets a label keep its frame.
@@ -672,7 +710,7 @@ int ttmi_stream_reserve_cus(void* stream, int n);
  * workgroups end with one atomically added piece per workgroup instead of a second round; without a reservation the launches stay free of atomics either way);
  * 21: 0 = the joint's sums over frames (dPD) by f32 atomics as in rounds 1 - 5 (default 1: partial rows + an ordered second pass - the same bits in every run, same time);
  * 22: 0 = bf16x3 weight gradients as three accumulating launches (round 5) instead of one launch over the plane pairs + a fold;
- * 23: ttmi_rnnt_align / ttmi_mono_align bits: 1 = decision words in the caller's workspace whatever the shape, 2 = forward walk only, no backtrace (frames of real labels are not written) */
+ * 23: ttmi_rnnt_align / ttmi_mono_align / ttmi_ctc_align bits: 1 = decision words in the caller's workspace whatever the shape, 2 = forward walk only, no backtrace (frames of real labels are not written) */
 int ttmi_set_option(int key, int value);
 int ttmi_dropout_apply(const float* in, long n, float p, unsigned seed, float* out, void* stream);
 int ttmi_probe_arm(int slot);

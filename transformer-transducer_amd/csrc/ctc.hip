@@ -334,9 +334,292 @@ __global__ __launch_bounds__(256) void ctc_greedy_kernel(const float* __restrict
     if (lane == 0) count[b] = bad != 0x7fffffff ? -(1 + bad) : n;
 }
 
+// ------------------------------------------------------------------ forced alignment: best path through the CTC lattice
+// v(0,0) = lp(0,0), v(0,1) = lp(0,1), v(t,s) = lp(t,s) + max(v(t-1,s), v(t-1,s-1), v(t-1,s-2)), the s-2 term under the skip rule of the loss.
+// It is the alpha half of ctc_alphabeta_kernel with max in place of lae, in the same shape: one workgroup per utterance, thread k owns the
+// state pair (2k, 2k+1), "label k-1" arrives by the one-lane DPP rotate, the cell that crosses a wave boundary goes through the
+// double-buffered LDS slot (U + 1 <= 64: one wave, no barrier in the walk), emission rows prefetched CTC_PF frames ahead, frontier in fp64.
+// TIE RULE: predecessors are tried in the order s, s-1, s-2 and a later one replaces an earlier one only when STRICTLY greater.
+// The decision of a blank state is one bit (1 = came from s-1), of a label state two (01 = s-1, 10 = s-2): three __ballot words per frame
+// and wave, 1.5 bits per cell, stored by lane 0 at dec[(t * W + wave) * 3 ...] - in LDS when the utterance's words fit, else in the caller's
+// workspace.  The backtrace follows in the same kernel on wave 0, serial per utterance: the path ends in S-1 unless v(T_b-1, S-2) is strictly
+// greater and steps one frame down per decision; the wave fetches the words of 64 frames at a time (lane j: frame t - j, the wave that owns
+// state s) and walks them by lane reads with t and s in scalar registers - a new fetch only after 64 steps or when s leaves that wave's
+// states.  s never grows and is clamped at 0, so whatever the workspace holds (NaN included) no index leaves its array.
+typedef unsigned long long cdec_t;
+constexpr int CTC_DW = 3;                 // decision words per (frame, wave): blank bit, label low bit, label high bit
+
+template <bool MULTI, bool LDS_DEC>
+__global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_viterbi_kernel(
+    const float* __restrict__ lp, const int* __restrict__ labels, const int* __restrict__ act_lens, const int* __restrict__ label_lens,
+    int T, int U, int V, int blank, cdec_t* __restrict__ dec_ws, int* __restrict__ path, int* __restrict__ spans,
+    float* __restrict__ score, int backtrace) {
+    extern __shared__ __attribute__((aligned(16))) char ctc_vit_smem[];
+    __shared__ acc_t bnd[2][16];          // the label cell that crosses a wave boundary, double-buffered by frame parity
+    __shared__ acc_t fin[2];
+    const int b = blockIdx.x;
+    const int k = threadIdx.x, lane = k & 63, wave = k >> 6, W = blockDim.x >> 6;
+    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U);
+    const bool vb = k <= Ub, vl = k < Ub;             // this thread's blank / label state exists
+    const int* lab = labels + (long)b * U;
+    const int yk = vl ? clampi(lab[k], 0, V - 1) : -1;
+    const long rp = ctc_sp(U) / 2;                    // pairs per frame
+    const int kc = k <= U ? k : U;                    // in-range pair for the (unconditional) loads of the threads that pad the last wave
+    const float2* e2 = reinterpret_cast<const float2*>(lp + (long)b * T * ctc_sp(U)) + kc;
+    cdec_t* dec_l = reinterpret_cast<cdec_t*>(ctc_vit_smem);                // [T_b][W][3] (LDS_DEC)
+    cdec_t* dec_g = dec_ws + (long)b * T * W * CTC_DW;                      // [T][W][3] per utterance (otherwise)
+    // skip transition into label state 2k+1 from 2k-1: l'_s != blank and l'_s != l'_{s-2}
+    const bool skip = vl && k > 0 && yk != blank && yk != clampi(lab[k > 0 ? k - 1 : 0], 0, V - 1);
+    float2 cur[CTC_PF], nxt[CTC_PF];
+    const float2 e0 = e2[0];
+    acc_t ab = k == 0 ? (acc_t)e0.x : (acc_t)NEG;
+    acc_t al = (k == 0 && vl) ? (acc_t)e0.y : (acc_t)NEG;
+#pragma unroll
+    for (int i = 0; i < CTC_PF; ++i) cur[i] = e2[(long)min(1 + i, Tb - 1) * rp];
+    for (int base = 1; base < Tb; base += CTC_PF) {
+#pragma unroll
+        for (int i = 0; i < CTC_PF; ++i) nxt[i] = e2[(long)min(base + CTC_PF + i, Tb - 1) * rp];
+#pragma unroll
+        for (int i = 0; i < CTC_PF; ++i) {
+            const int t = base + i;
+            if (t < Tb) {                              // workgroup-uniform
+                if (MULTI) {
+                    if (lane == 63) bnd[t & 1][wave] = al;
+                    __syncthreads();
+                }
+                acc_t nb = rot_r1(al);                 // label state of thread k-1 at frame t-1
+                if (lane == 0) nb = (MULTI && wave > 0) ? bnd[t & 1][wave > 0 ? wave - 1 : 0] : (acc_t)NEG;
+                const bool db = vb && k > 0 && nb > ab;                    // blank state: s, then s-1
+                const acc_t nab = vb ? (acc_t)cur[i].x + (db ? nb : ab) : (acc_t)NEG;
+                acc_t m = al;                                              // label state: s, then s-1, then s-2
+                const bool d1 = vl && ab > m;
+                m = d1 ? ab : m;
+                const bool d2 = skip && nb > m;
+                m = d2 ? nb : m;
+                al = vl ? (acc_t)cur[i].y + m : (acc_t)NEG;
+                ab = nab;
+                const cdec_t w0 = __ballot(db), w1 = __ballot(d1 && !d2), w2 = __ballot(d2);
+                if (lane == 0) {
+                    const long o = ((long)t * W + wave) * CTC_DW;
+                    if constexpr (LDS_DEC) { dec_l[o] = w0; dec_l[o + 1] = w1; dec_l[o + 2] = w2; }
+                    else { dec_g[o] = w0; dec_g[o + 1] = w1; dec_g[o + 2] = w2; }
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < CTC_PF; ++i) cur[i] = nxt[i];
+    }
+    // the path ends in S-1 = 2 U_b (thread U_b's blank) unless S-2 (thread U_b - 1's label) is strictly greater
+    if (k == Ub) fin[0] = ab;
+    if (Ub > 0 && k == Ub - 1) fin[1] = al;
+    if constexpr (!LDS_DEC) __threadfence();
+    __syncthreads();                                   // ... and lane 0's decision words are visible to wave 0
+    const acc_t endb = fin[0], endl = Ub > 0 ? fin[1] : (acc_t)NEG;
+    const bool end_lab = Ub > 0 && endl > endb;
+    const acc_t best = end_lab ? endl : endb;
+    const bool dead = best <= CTC_DEAD;                // no feasible alignment, by the loss's threshold (a NaN stays a NaN)
+    int* pr = path + (long)b * T;
+    int* sp = spans + (long)b * U * 2;
+    for (int t = (dead ? 0 : Tb) + k; t < T; t += blockDim.x) pr[t] = -1;
+    for (int i = (dead ? 0 : 2 * Ub) + k; i < 2 * U; i += blockDim.x) sp[i] = -1;
+    if (k == 0) score[b] = dead ? -INFINITY : (float)best;
+    if (dead || !backtrace || wave != 0) return;       // (ttmi_set_option(23, 2): the forward walk alone, measurement only)
+    int t = Tb - 1, s = end_lab ? 2 * Ub - 1 : 2 * Ub;
+    int last = t;                                      // last frame of the run of states the walk is in
+    while (t >= 0) {
+        const int g = s >> 7;                          // the wave that owns state s
+        const int tl = t - lane;
+        cdec_t w[CTC_DW] = {0, 0, 0};
+        if (tl >= 1) {                                 // frame 0 has no predecessor and no words
+            const long o = ((long)tl * W + g) * CTC_DW;
+#pragma unroll
+            for (int i = 0; i < CTC_DW; ++i) {
+                if constexpr (LDS_DEC) w[i] = dec_l[o + i];
+                else w[i] = dec_g[o + i];
+            }
+        }
+        int lo[CTC_DW], hi[CTC_DW];
+#pragma unroll
+        for (int i = 0; i < CTC_DW; ++i) {
+            lo[i] = (int)(unsigned)(w[i] & 0xffffffffULL);
+            hi[i] = (int)(unsigned)(w[i] >> 32);
+        }
+        const int t0 = t;
+        int mine = -1, j = 0;
+        for (; j < 64 && t >= 0 && (s >> 7) == g; ++j, --t) {
+            mine = lane == j ? s : mine;
+            const int q = (s >> 1) & 63;
+            auto bit = [&](int i) -> int {
+                const unsigned x = (unsigned)((q & 32) ? __builtin_amdgcn_readlane(hi[i], j) : __builtin_amdgcn_readlane(lo[i], j));
+                return (int)((x >> (q & 31)) & 1u);
+            };
+            int d = 0;
+            if (t > 0) d = (s & 1) ? bit(1) + 2 * bit(2) : bit(0);
+            if (d > s) d = s;
+            if (d != 0 || t == 0) {                    // frame t opens the run: a label state's span is (t, last)
+                if ((s & 1) && lane == 0) {
+                    sp[s - 1] = t;
+                    sp[s] = last;
+                }
+                last = t - 1;
+            }
+            s -= d;
+        }
+        if (lane < j) pr[t0 - lane] = mine;
+    }
+}
+
+// Per label, from a finished forward: the occupancy g(t,s) = exp(alpha(t,s) + beta(t,s) - lp(t,s) - ll) of its state s = 2u+1 and the
+// posterior e(t,u) that its run starts at frame t - e(t,u) = exp(logsumexp(alpha(t-1,s-1), alpha(t-1,s-2) [skip rule]) + beta(t,s) - ll) for
+// t > 0 (beta includes the emission at t), e(0,0) = g(0,1), e(0,u>0) = 0.  mass = sum_t e (every alignment enters every label state exactly
+// once: 1, a health check of the lattice), expected = sum_t t e, duration = sum_t g.  One workgroup per (utterance, 64 labels), lanes across
+// u, so every load of the time-major tables is one row segment.  The TERMS of a chunk of 32 frames are formed by all eight waves (four frames
+// each, their loads in flight together: the kernel is bound by load latency) and handed over in LDS as the f32 values the exponential
+// returns; the SUMS have one owner, lane u of wave 0, which adds the chunk's terms in frame order in fp64 - the order of a serial loop over
+// t, whatever the wave count.  The hand-over is double-buffered by chunk parity: one barrier per chunk.  No atomics.  Entries u >= U_b and
+// utterances without a feasible alignment: mass 0, expected -1, duration 0.
+constexpr int CTC_ES_WAVES = 8, CTC_ES_F = 4, CTC_ES_CHUNK = CTC_ES_WAVES * CTC_ES_F;
+
+__global__ __launch_bounds__(CTC_ES_WAVES * 64) void ctc_emit_stats_kernel(
+    const acc_t* __restrict__ alpha, const acc_t* __restrict__ beta, const acc_t* __restrict__ ll, const float* __restrict__ lp,
+    const int* __restrict__ labels, const int* __restrict__ act_lens, const int* __restrict__ label_lens, int T, int U, int V, int blank,
+    int G, float* __restrict__ expected, float* __restrict__ mass, float* __restrict__ duration) {
+    __shared__ float2 part[2][CTC_ES_CHUNK][64];       // (e, g) of a chunk's frames
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.x / G;
+    const int u = (blockIdx.x % G) * 64 + lane;
+    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U);
+    const acc_t L = ll[b];
+    const bool live = L > CTC_DEAD;                    // workgroup-uniform
+    const bool has = live && u < Ub;
+    acc_t m = 0.0, e1 = 0.0, dur = 0.0;
+    if (live) {
+        const int uc = has ? u : 0;                    // lanes without a label form in-range addresses and load nothing
+        const int* lab = labels + (long)b * U;
+        const int yu = has ? clampi(lab[uc], 0, V - 1) : -1;
+        const bool skip = has && u > 0 && yu != blank && yu != clampi(lab[uc > 0 ? uc - 1 : 0], 0, V - 1);
+        const long rp = ctc_sp(U) / 2;
+        const double2* a2 = reinterpret_cast<const double2*>(alpha + (long)b * T * ctc_sp(U)) + uc;
+        const double2* b2 = reinterpret_cast<const double2*>(beta + (long)b * T * ctc_sp(U)) + uc;
+        const float2* e2 = reinterpret_cast<const float2*>(lp + (long)b * T * ctc_sp(U)) + uc;
+        for (int base = 0, c = 0; base < Tb; base += CTC_ES_CHUNK, ++c) {
+            float2 v[CTC_ES_F];
+#pragma unroll
+            for (int i = 0; i < CTC_ES_F; ++i) {
+                const int t = base + wv * CTC_ES_F + i;
+                v[i] = make_float2(0.f, 0.f);
+                if (has && t < Tb) {
+                    const long o = (long)t * rp;
+                    const acc_t bt = b2[o].y;
+                    const float g = __expf((float)(a2[o].y + bt - (acc_t)e2[o].y - L));
+                    float e = u == 0 ? g : 0.f;        // frame 0: e(0,0) = g(0,1), e(0,u>0) = 0
+                    if (t > 0) {
+                        acc_t in = a2[o - rp].x;       // alpha(t-1, 2u)
+                        if (skip) in = lae(in, a2[o - rp - 1].y);      // alpha(t-1, 2u-1): the label state of pair u-1
+                        e = __expf((float)(in + bt - L));
+                    }
+                    v[i] = make_float2(e, g);
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < CTC_ES_F; ++i) part[c & 1][wv * CTC_ES_F + i][lane] = v[i];
+            __syncthreads();
+            if (wv == 0) {
+                const int n = min(CTC_ES_CHUNK, Tb - base);
+                for (int f = 0; f < n; ++f) {
+                    const float2 x = part[c & 1][f][lane];
+                    m += (acc_t)x.x;
+                    e1 += (acc_t)(base + f) * (acc_t)x.x;
+                    dur += (acc_t)x.y;
+                }
+            }
+        }
+    }
+    if (wv == 0 && u < U) {
+        const long i = (long)b * U + u;
+        mass[i] = has ? (float)m : 0.f;
+        expected[i] = has ? (float)e1 : -1.f;
+        duration[i] = has ? (float)dur : 0.f;
+    }
+}
+
+constexpr size_t CTC_VIT_LDS_MAX = 128 * 1024;        // rnnt.hip's VIT_LDS_MAX: decision words of one utterance kept in LDS up to here (of the CU's 160 KB)
+__host__ __forceinline__ size_t ctc_dec_bytes(int T, int U) { return (size_t)T * ((U + 1 + 63) / 64) * CTC_DW * sizeof(cdec_t); }
+
+template <bool MULTI>
+int ctc_launch_viterbi(hipStream_t st, int B, int threads, const CtcWs& w, const int* labels, const int* al, const int* ll_, int T, int U, int V,
+                       int blank, cdec_t* dec_ws, int* path, int* spans, float* score, int debug) {
+    const size_t lds = ctc_dec_bytes(T, U);
+    const int backtrace = (debug & 2) ? 0 : 1;
+    if (lds <= CTC_VIT_LDS_MAX && !(debug & 1)) {
+        if (lds > 64 * 1024) {
+            // above the default limit the attribute is needed, and it belongs to the current DEVICE: it is set on every such call (a host-side
+            // call, no stream work) instead of being remembered per process
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_viterbi_kernel<MULTI, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CTC_VIT_LDS_MAX);
+            if (e != hipSuccess) {
+                ttmi_set_error("ctc align: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
+                return (int)e;
+            }
+        }
+        hipLaunchKernelGGL((ctc_viterbi_kernel<MULTI, true>), dim3(B), dim3(threads), lds, st, w.lp, labels, al, ll_, T, U, V, blank, dec_ws, path,
+                           spans, score, backtrace);
+    } else {
+        hipLaunchKernelGGL((ctc_viterbi_kernel<MULTI, false>), dim3(B), dim3(threads), 0, st, w.lp, labels, al, ll_, T, U, V, blank, dec_ws, path,
+                           spans, score, backtrace);
+    }
+    return TTMI_OK;
+}
+
 }  // namespace
 
+int ttmi_rnnt_get_align_debug();          // rnnt.hip: ttmi_set_option(23, bits), shared with ttmi_rnnt_align / ttmi_mono_align
+
 extern "C" {
+
+// Forced alignment and emission statistics from the workspace a finished ttmi_ctc_loss_fwd left on the same (B, T, U); that workspace is
+// only read (include/ttmi.h).  No host synchronisation, no memset node: both are capturable in a HIP graph.
+size_t ttmi_ctc_align_workspace_bytes(int B, int T, int U) {
+    if (B <= 0 || T <= 0 || U < 0 || U > 1023) return 0;
+    return (size_t)B * ctc_dec_bytes(T, U);
+}
+
+int ttmi_ctc_align(const void* workspace, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U, int V, int blank,
+                   void* align_workspace, int* path, int* spans, float* score, void* stream) {
+    TTMI_REQUIRE(workspace && (labels || U == 0) && act_lens && label_lens && align_workspace && path && (spans || U == 0) && score,
+                 "ctc_align: null pointer");
+    TTMI_REQUIRE(B > 0 && T > 0 && U >= 0 && V >= 2, "ctc_align: bad shape B=%d T=%d U=%d V=%d", B, T, U, V);
+    TTMI_REQUIRE(U <= 1023, "ctc_align: U=%d > 1023 unsupported", U);
+    TTMI_REQUIRE(blank >= 0 && blank < V, "ctc_align: blank %d outside [0,%d)", blank, V);
+    TTMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ctc_align: workspace must be 16-byte aligned");
+    TTMI_REQUIRE((reinterpret_cast<uintptr_t>(align_workspace) & 7) == 0, "ctc_align: align_workspace must be 8-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const CtcWs w = ctc_carve(const_cast<void*>(workspace), B, T, U);
+    cdec_t* dec = static_cast<cdec_t*>(align_workspace);
+    const int debug = ttmi_rnnt_get_align_debug();
+    const int threads = cdiv(U + 1, 64) * 64;
+    int rc;
+    if (threads == 64) rc = ctc_launch_viterbi<false>(st, B, threads, w, labels, act_lens, label_lens, T, U, V, blank, dec, path, spans, score, debug);
+    else rc = ctc_launch_viterbi<true>(st, B, threads, w, labels, act_lens, label_lens, T, U, V, blank, dec, path, spans, score, debug);
+    if (rc) return rc;
+    TTMI_LAUNCH_CHECK("ctc_viterbi_kernel");
+    return TTMI_OK;
+}
+
+int ttmi_ctc_emit_stats(const void* workspace, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U, int V,
+                        int blank, float* expected, float* mass, float* duration, void* stream) {
+    TTMI_REQUIRE(workspace && act_lens && label_lens && ((labels && expected && mass && duration) || U == 0), "ctc_emit_stats: null pointer");
+    TTMI_REQUIRE(B > 0 && T > 0 && U >= 0 && V >= 2, "ctc_emit_stats: bad shape B=%d T=%d U=%d V=%d", B, T, U, V);
+    TTMI_REQUIRE(U <= 1023, "ctc_emit_stats: U=%d > 1023 unsupported", U);
+    TTMI_REQUIRE(blank >= 0 && blank < V, "ctc_emit_stats: blank %d outside [0,%d)", blank, V);
+    TTMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ctc_emit_stats: workspace must be 16-byte aligned");
+    if (U == 0) return TTMI_OK;           // no labels: nothing to write
+    const CtcWs w = ctc_carve(const_cast<void*>(workspace), B, T, U);
+    const int G = cdiv(U, 64);
+    hipLaunchKernelGGL(ctc_emit_stats_kernel, dim3((unsigned)((long)B * G)), dim3(CTC_ES_WAVES * 64), 0, static_cast<hipStream_t>(stream), w.alpha, w.beta, w.ll,
+                       w.lp, labels, act_lens, label_lens, T, U, V, blank, G, expected, mass, duration);
+    TTMI_LAUNCH_CHECK("ctc_emit_stats_kernel");
+    return TTMI_OK;
+}
 
 // bytes of caller-provided workspace shared by ttmi_ctc_loss_fwd / _bwd (16-byte aligned): lp table, alpha, beta, ll, lse, symbol chains
 size_t ttmi_ctc_workspace_bytes(int B, int T, int U) {

@@ -1029,6 +1029,28 @@ class Transducer(nn.Module):
         lens = None if inputs_length is None else torch.as_tensor(inputs_length).to(enc_state.device)
         return ctc_greedy_decode(logits, lens, blank=0)
 
+    @torch.no_grad()
+    def align_ctc(self, inputs, inputs_length, targets, targets_length, *, stats=False):
+        """Forced alignment of `targets` to `inputs` on the CTC lattice of the auxiliary head (blank = 0): the audio encoder once, the head,
+        then ttmi.ctc.ctc_align -> ttmi.ctc.CTCAlignment: `path` int32 [B, T] (state of the extended label sequence per frame), `spans`
+        int32 [B, U, 2] ((first, last) frame of each label, -1 for u >= U_b), `score` [B] (log-probability of the best alignment) and, with
+        stats=True, `expected` / `mass` / `duration` [B, U] (expected onset frame, onset mass - 1 for a healthy lattice - and expected
+        number of frames of each label over all alignments).  The head's posteriors come from the audio encoder alone: compare `expected`
+        with align(..., stats=True).expected_frames for the emission delay of the two heads.  ValueError on a module without the head."""
+        from ttmi.ctc import ctc_align
+        if getattr(self, "ctc_head", None) is None:
+            raise ValueError("this Transducer has no CTC head: build it with config.ctc_weight > 0")
+        if not inputs.is_cuda:
+            raise ValueError("Transducer.align_ctc: inputs must live on the GPU (the MI355X build has no CPU path)")
+        enc_state = self.encoder(inputs, self._audio_mask(inputs)).contiguous()
+        B, T, d = enc_state.shape
+        V = self.ctc_head.out_features
+        buf, logits = ops.padded_empty((B, T, V), torch.float32, enc_state.device)
+        ops.weights_fresh()
+        ops.linear_nt(enc_state.reshape(B * T, d), self.ctc_head.weight.detach(), buf.view(B * T, buf.shape[-1])[:, :V],
+                      bias=self.ctc_head.bias.detach(), prec=default_precision())
+        return ctc_align(logits, targets, inputs_length, targets_length, blank=0, stats=stats)
+
     def align(self, inputs, inputs_length, targets, targets_length, chunk=None, check_lengths=True, exp_domain=False, *, stats=False):
         """Forced alignment of `targets` to `inputs`: the best path through the RNN-T lattice, without materialising the logits (the chunked
         joint + loss forward of `loss()`, forward only, under no_grad; the reference has no counterpart).  -> warprnnt_pytorch.AlignResult:

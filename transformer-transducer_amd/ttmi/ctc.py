@@ -4,11 +4,15 @@ For joint CTC - transducer training: a linear head on the audio encoder's output
 (`Transducer.loss(..., ctc_weight=w)`), and its argmax with repeats collapsed is a non-autoregressive recogniser
 (`Transducer.recognize_ctc`).  There is no CPU path.
 """
+import collections
+
 import torch
 
 from . import ops
 
-__all__ = ["CTCLoss", "ctc_loss", "ctc_greedy_decode"]
+__all__ = ["CTCLoss", "ctc_loss", "ctc_greedy_decode", "ctc_align", "CTCAlignment"]
+
+CTCAlignment = collections.namedtuple("CTCAlignment", "path spans score expected mass duration")
 
 
 def _lengths(logits, labels, act_lens, label_lens):
@@ -112,3 +116,32 @@ def ctc_greedy_decode(logits, act_lens=None, blank=0):
             raise RuntimeError("CTC greedy decode: the head produced no finite maximum at frame %d of utterance %d (NaN logits?)" % (-n - 1, b))
         out.append(host[b, 1:1 + n].tolist())
     return out
+
+
+@torch.no_grad()
+def ctc_align(logits, labels, act_lens, label_lens, blank=0, stats=False):
+    """Forced alignment of `labels` on the CTC lattice of `logits` (f32 [B, T, V] on the GPU, un-normalised; lengths checked and clamped as
+    by ctc_loss) -> CTCAlignment(path, spans, score, expected, mass, duration), all on the device:
+
+    path      int32 [B, T]     the state of the extended label sequence (2u = the blank before label u, 2u+1 = label u) the best single
+                               alignment sits in at every frame, -1 for t >= T_b
+    spans     int32 [B, U, 2]  (first, last) frame of label u on that alignment, (-1, -1) for u >= U_b
+    score     f32 [B]          its log-probability; -inf, with every path / spans entry -1, where no alignment is feasible
+    expected  f32 [B, U]       stats=True: the expected onset frame of label u over ALL alignments (-1 for u >= U_b), else None
+    mass      f32 [B, U]       stats=True: the total onset posterior, 1 for a healthy lattice (0 for u >= U_b), else None
+    duration  f32 [B, U]       stats=True: the expected number of frames label u occupies (0 for u >= U_b), else None
+
+    Forward only: the loss forward into a workspace of its own, then ttmi_ctc_align (and ttmi_ctc_emit_stats); include/ttmi.h has the
+    recurrences and the tie rule.  No host synchronisation."""
+    labels, act_lens, label_lens = _lengths(logits, labels, act_lens, label_lens)
+    x = logits.detach()
+    if x.dtype is not torch.float32 or ops.row_pitch(x) is None:
+        x = x.float().contiguous()
+    B, T, V = x.shape
+    ws = ops.ctc_workspace(B, T, labels.shape[1], x.device)
+    ops.ctc_loss_fwd(x, labels, act_lens, label_lens, int(blank), ws)
+    path, spans, score = ops.ctc_align(ws, labels, act_lens, label_lens, B, T, V, int(blank))
+    expected = mass = duration = None
+    if stats:
+        expected, mass, duration = ops.ctc_emit_stats(ws, labels, act_lens, label_lens, B, T, V, int(blank))
+    return CTCAlignment(path, spans, score, expected, mass, duration)

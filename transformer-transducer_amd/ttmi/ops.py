@@ -368,6 +368,48 @@ def ctc_greedy(logits, act_lens, blank=0):
     return tokens, count
 
 
+def ctc_align_workspace(B, T, U, device):
+    """scratch of ctc_align (decision words when they do not fit LDS): int64 words, never empty (the entry wants a pointer whatever the shape)"""
+    f = lib().ttmi_ctc_align_workspace_bytes
+    f.restype = ctypes.c_size_t
+    n = f(c_int(B), c_int(T), c_int(U))
+    return torch.empty(max((n + 7) // 8, 1), dtype=torch.int64, device=device)
+
+
+def ctc_align(workspace, labels, act_lens, label_lens, B, T, V, blank=0, align_workspace=None):
+    """the best path through the lattice a finished ctc_loss_fwd left in `workspace` (read only); labels int32 [B, U] -> (path int32 [B, T]:
+    the state index of l' at every frame, -1 for t >= T_b; spans int32 [B, U, 2]: (first, last) frame of label u, -1 for u >= U_b; score
+    f32 [B]: the path's log-probability).  An utterance with no feasible alignment: score -inf, every path / spans entry -1.  Predecessors
+    are tried in the order s, s-1, s-2 and replaced only when strictly greater (include/ttmi.h, ttmi_ctc_align)"""
+    _need_cuda(workspace, labels, act_lens, label_lens)
+    if labels.dim() != 2 or labels.shape[0] != B or labels.dtype is not torch.int32 or (labels.numel() and not labels.is_contiguous()):
+        raise ValueError("ctc: labels must be contiguous int32 [B, U]")
+    U = labels.shape[1]
+    _trace("ctc_align", B, T, U)
+    aws = ctc_align_workspace(B, T, U, workspace.device) if align_workspace is None else align_workspace
+    path = torch.empty(B, T, dtype=torch.int32, device=workspace.device)
+    spans = torch.empty(B, U, 2, dtype=torch.int32, device=workspace.device)
+    score = torch.empty(B, dtype=torch.float32, device=workspace.device)
+    check(lib().ttmi_ctc_align(_p(workspace), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U), c_int(V), c_int(blank),
+                               _p(aws), _p(path), _p(spans), _p(score), _stream()), "ttmi_ctc_align")
+    return path, spans, score
+
+
+def ctc_emit_stats(workspace, labels, act_lens, label_lens, B, T, V, blank=0):
+    """from the alpha / beta of a finished ctc_loss_fwd in `workspace` (read only) -> (expected f32 [B, U]: expected onset frame of label u,
+    -1 for u >= U_b; mass f32 [B, U]: total onset posterior, 1 for a healthy lattice; duration f32 [B, U]: expected number of frames the
+    label occupies); an utterance with no feasible alignment has -1 / 0 / 0 in every entry (include/ttmi.h, ttmi_ctc_emit_stats)"""
+    _need_cuda(workspace, labels, act_lens, label_lens)
+    if labels.dim() != 2 or labels.shape[0] != B or labels.dtype is not torch.int32 or (labels.numel() and not labels.is_contiguous()):
+        raise ValueError("ctc: labels must be contiguous int32 [B, U]")
+    U = labels.shape[1]
+    _trace("ctc_emit_stats", B, T, U)
+    expected, mass, duration = (torch.empty(B, U, dtype=torch.float32, device=workspace.device) for _ in range(3))
+    check(lib().ttmi_ctc_emit_stats(_p(workspace), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U), c_int(V),
+                                    c_int(blank), _p(expected), _p(mass), _p(duration), _stream()), "ttmi_ctc_emit_stats")
+    return expected, mass, duration
+
+
 def linear_nt(x, w, out, bias=None, prec=0, accumulate=False):
     """out[M, N] (f32, row pitch = out.stride(0)) (+)= x[M, K] @ w[N, K]^T (+ bias): the library's generic GEMM on f32 operands - exact-f32
     MFMA in the fp32 mode, the three-term bf16 split in the bf16x3 mode, bf16 MFMA with f32 accumulation and output in the bf16 mode"""
