@@ -3,7 +3,7 @@
 //
 //   ctc_link_kernel       per utterance: which label positions carry the same symbol (a chain from the first occurrence through the
 //                         later ones), so that the gradient's sum over the states of one symbol has ONE owner and a fixed order.
-//   ctc_lse_kernel        HBM-bound: one wave per (b,t) row of V logits, the 16-byte online log-sum-exp walk of rnnt_lse_kernel; gathers
+//   ctc_lse_kernel        HBM-bound: one wave per (b,t) row of V logits, lattice.h's row_lse walk; gathers
 //                         lp(t, s) = log_softmax(z[b,t])[l'_s] for the 2 U_b + 1 states of the extended label sequence.
 //   ctc_alphabeta_kernel  latency-bound dynamic programme: one workgroup per (utterance, direction), ONE launch for all T frames.  Thread
 //                         k owns the state pair (2k, 2k+1) = (blank before label k, label k): the s-1 neighbour of the label state is the
@@ -85,29 +85,8 @@ __global__ __launch_bounds__(CTC_ROW_WAVES * 64) void ctc_lse_kernel(
     const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U);
     if (t >= Tb) return;
     const float* r = logits + row * ldv;
-    float m = NEG, s = 0.f;
-    auto upd = [&](float x) {
-        const float mn = fmaxf(m, x);
-        s = s * __expf(m - mn) + __expf(x - mn);
-        m = mn;
-    };
-    const int head = row_head<float>(r, V, vec_ok);
-    for (int i = lane; i < head; i += 64) upd(r[i]);
-    const int nvec = (V - head) / 4;
-    for (int i = lane; i < nvec; i += 64) {
-        Vec16<float> x;
-        x.template load<false>(r + head + i * 4);
-        const float mx = fmaxf(fmaxf(x.f[0], x.f[1]), fmaxf(x.f[2], x.f[3]));
-        const float mn = fmaxf(m, mx);
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc += __expf(x.f[k] - mn);
-        s = s * __expf(m - mn) + acc;
-        m = mn;
-    }
-    for (int i = head + nvec * 4 + lane; i < V; i += 64) upd(r[i]);
-    const float M = wave_max(m);
-    s = wave_sum(s * __expf(m - M));
+    float M, s;
+    row_lse<float>(r, V, vec_ok, lane, M, s);
     const float l = M + __logf(s);
     if (lane == 0) lse[row] = l;
     // the row's 2 U_b + 1 emission log-probs (the row is in cache: it has just been read); clamped at NEG so that a -inf logit is a dead
@@ -245,20 +224,8 @@ __global__ __launch_bounds__(CTC_ROW_WAVES * 64) void ctc_grad_kernel(
         l = lse[row];
         gs = scale * grad_out[(long)b * grad_out_stride];
     }
-    auto f = [&](float x) -> float { return live ? gs * __expf(x - l) : 0.f; };
-    const int head = row_head<float>(r, V, vec_ok);
-    for (int i = lane; i < head; i += 64) g[i] = f(live ? r[i] : 0.f);
-    const int nvec = (V - head) / 4;
-    for (int i = lane; i < nvec; i += 64) {
-        Vec16<float> x;
-        const int v0 = head + i * 4;
-        if (live) x.load(r + v0);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) x.f[k] = f(live ? x.f[k] : 0.f);
-        x.store(g + v0);
-    }
-    for (int i = head + nvec * 4 + lane; i < V; i += 64) g[i] = f(live ? r[i] : 0.f);
-    for (int i = V + lane; i < ldg; i += 64) g[i] = 0.f;      // padded pitch: the head's dgrad / wgrad GEMMs may run over the full pitch
+    // g * softmax over the whole row; the pad columns are zeroed: the head's dgrad / wgrad GEMMs may run over the full pitch
+    row_map<float>(r, g, V, ldg, vec_ok, lane, live, [&](float x, int) -> float { return live ? gs * __expf(x - l) : 0.f; });
     if (!live) return;                                          // (wave-uniform)
     // the columns of the row's own symbols: g * (softmax - sum over the states of that symbol of exp(alpha + beta - lp - ll)).  The wave's
     // softmax stores above are complete before these overwrite them; each column has ONE owner lane that adds its states in label order.
@@ -543,32 +510,7 @@ __global__ __launch_bounds__(CTC_ES_WAVES * 64) void ctc_emit_stats_kernel(
     }
 }
 
-constexpr size_t CTC_VIT_LDS_MAX = 128 * 1024;        // rnnt.hip's VIT_LDS_MAX: decision words of one utterance kept in LDS up to here (of the CU's 160 KB)
 __host__ __forceinline__ size_t ctc_dec_bytes(int T, int U) { return (size_t)T * ((U + 1 + 63) / 64) * CTC_DW * sizeof(cdec_t); }
-
-template <bool MULTI>
-int ctc_launch_viterbi(hipStream_t st, int B, int threads, const CtcWs& w, const int* labels, const int* al, const int* ll_, int T, int U, int V,
-                       int blank, cdec_t* dec_ws, int* path, int* spans, float* score, int debug) {
-    const size_t lds = ctc_dec_bytes(T, U);
-    const int backtrace = (debug & 2) ? 0 : 1;
-    if (lds <= CTC_VIT_LDS_MAX && !(debug & 1)) {
-        if (lds > 64 * 1024) {
-            // above the default limit the attribute is needed, and it belongs to the current DEVICE: it is set on every such call (a host-side
-            // call, no stream work) instead of being remembered per process
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_viterbi_kernel<MULTI, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)CTC_VIT_LDS_MAX);
-            if (e != hipSuccess) {
-                ttmi_set_error("ctc align: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-                return (int)e;
-            }
-        }
-        hipLaunchKernelGGL((ctc_viterbi_kernel<MULTI, true>), dim3(B), dim3(threads), lds, st, w.lp, labels, al, ll_, T, U, V, blank, dec_ws, path,
-                           spans, score, backtrace);
-    } else {
-        hipLaunchKernelGGL((ctc_viterbi_kernel<MULTI, false>), dim3(B), dim3(threads), 0, st, w.lp, labels, al, ll_, T, U, V, blank, dec_ws, path,
-                           spans, score, backtrace);
-    }
-    return TTMI_OK;
-}
 
 }  // namespace
 
@@ -597,9 +539,12 @@ int ttmi_ctc_align(const void* workspace, const int* labels, const int* act_lens
     cdec_t* dec = static_cast<cdec_t*>(align_workspace);
     const int debug = ttmi_rnnt_get_align_debug();
     const int threads = cdiv(U + 1, 64) * 64;
-    int rc;
-    if (threads == 64) rc = ctc_launch_viterbi<false>(st, B, threads, w, labels, act_lens, label_lens, T, U, V, blank, dec, path, spans, score, debug);
-    else rc = ctc_launch_viterbi<true>(st, B, threads, w, labels, act_lens, label_lens, T, U, V, blank, dec, path, spans, score, debug);
+    auto launch = [&](auto k_lds, auto k_ws) {
+        return launch_dec_lds("ctc align", k_lds, k_ws, ctc_dec_bytes(T, U), debug, dim3(B), dim3(threads), st, w.lp, labels, act_lens, label_lens, T,
+                              U, V, blank, dec, path, spans, score);
+    };
+    const int rc = threads == 64 ? launch(ctc_viterbi_kernel<false, true>, ctc_viterbi_kernel<false, false>)
+                                 : launch(ctc_viterbi_kernel<true, true>, ctc_viterbi_kernel<true, false>);
     if (rc) return rc;
     TTMI_LAUNCH_CHECK("ctc_viterbi_kernel");
     return TTMI_OK;
@@ -639,7 +584,7 @@ int ttmi_ctc_loss_fwd(const float* logits, long ldv, const int* labels, const in
     hipStream_t st = static_cast<hipStream_t>(stream);
     CtcWs w = ctc_carve(workspace, B, T, U);
     const long rows = (long)B * T;
-    const int vec_ok = ((reinterpret_cast<uintptr_t>(logits) % 4) == 0) ? 1 : 0;
+    const int vec_ok = rows_vec_ok(logits, 4);
     if (U > 0) {
         hipLaunchKernelGGL(ctc_link_kernel, dim3(B), dim3(256), 0, st, labels, label_lens, U, V, blank, w.link);
         TTMI_LAUNCH_CHECK("ctc_link_kernel");
@@ -671,9 +616,7 @@ int ttmi_ctc_loss_bwd(const float* logits, long ldv, const int* labels, const in
     hipStream_t st = static_cast<hipStream_t>(stream);
     CtcWs w = ctc_carve(const_cast<void*>(workspace), B, T, U);
     const long rows = (long)B * T;
-    // vector path needs logits and grad rows to share their 16-byte phase
-    const int vec_ok = ((reinterpret_cast<uintptr_t>(logits) % 16) == (reinterpret_cast<uintptr_t>(grad) % 16) && ((ldv - ldg) * 4L) % 16 == 0 &&
-                        (reinterpret_cast<uintptr_t>(logits) % 4) == 0) ? 1 : 0;
+    const int vec_ok = rows_vec_ok(logits, grad, ldv, ldg, 4);
     hipLaunchKernelGGL(ctc_grad_kernel, dim3(cdiv(rows, CTC_ROW_WAVES)), dim3(CTC_ROW_WAVES * 64), 0, st, logits, ldv, labels, act_lens,
                        label_lens, B, T, U, V, blank, vec_ok, w.lse, w.lp, w.alpha, w.beta, w.ll, w.link, grad_out, grad_out_stride, scale,
                        grad, ldg);

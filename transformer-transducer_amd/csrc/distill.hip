@@ -2,7 +2,7 @@
 // distribution over V outputs is collapsed to three classes - blank, the next label y_{u+1}, everything else - and the student is trained
 // with the KL divergence from the teacher's three to its own three (include/ttmi.h has the arithmetic).  No reference counterpart.
 //
-//   kd_row_kernel    HBM-bound: one wave per (b,t,u) row of V logits, the 16-byte online log-sum-exp walk of mono_lse_kernel - taken over the
+//   kd_row_kernel    HBM-bound: one wave per (b,t,u) row of V logits, lattice.h's row_lse walk - taken over the
 //                    columns OUTSIDE {blank, y} only, so the "other" mass is a log-sum-exp of its own and never 1 - p_b - p_y; the row's lse is
 //                    that sum joined with the two columns left out (three terms, lane 0).  TEACHER = false writes the collapsed posteriors,
 //                    TEACHER = true reads the teacher's and writes the row's record (lse, c_o, P^T_b, P^T_y) and its cost.
@@ -38,16 +38,13 @@ __global__ __launch_bounds__(KD_WAVES * 64) void kd_row_kernel(
     const TL* __restrict__ logits, long ldv, const int* __restrict__ labels, const int* __restrict__ act_lens,
     const int* __restrict__ label_lens, int B, int T, int U1, int V, int blank, int vec_ok, const float* __restrict__ teacher,
     float* __restrict__ post, float4* __restrict__ rec, float* __restrict__ cost) {
-    constexpr int NV = 16 / sizeof(TL);
+    constexpr int NV = Vec16<TL>::NV;
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * KD_WAVES + (threadIdx.x >> 6);
     if (row >= (long)B * T * U1) return;
-    const int u = (int)(row % U1);
-    const long bt = row / U1;
-    const int t = (int)(bt % T);
-    const int b = (int)(bt / T);
-    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U1 - 1);
-    if (t >= Tb || u > Ub) {
+    const LatticeRow p = lattice_row(row, T, U1, act_lens, label_lens);
+    const int b = p.b, u = p.u, Ub = p.Ub;
+    if (!p.inside()) {
         // the posteriors are a tensor the caller keeps: exact zeros outside the ragged lattice; the student's records there are never read
         if constexpr (!TEACHER)
             if (lane < 3) post[row * 3 + lane] = 0.f;
@@ -59,39 +56,16 @@ __global__ __launch_bounds__(KD_WAVES * 64) void kd_row_kernel(
         if (yv == blank) yv = -1;
     }
     const TL* r = logits + row * ldv;
-    float m = NEG, s = 0.f;
     // a column of {blank, y} enters as -inf: exp(-inf - mn) = 0 whatever the running maximum (which never falls below NEG)
     auto other = [&](float x, int v) -> float { return (v == blank || v == yv) ? -INFINITY : x; };
-    auto upd = [&](float x) {
-        const float mn = fmaxf(m, x);
-        s = s * __expf(m - mn) + __expf(x - mn);
-        m = mn;
-    };
-    const int head = row_head<TL>(r, V, vec_ok);
-    for (int i = lane; i < head; i += 64) upd(other(ldf<TL>(r + i), i));
-    const int nvec = (V - head) / NV;
-    for (int i = lane; i < nvec; i += 64) {
-        Vec16<TL> x;
-        const int v0 = head + i * NV;
-        x.template load<false>(r + v0);
+    float M, s;
+    row_lse<TL>(r, V, vec_ok, lane, M, s, other, [&](Vec16<TL>& x, int v0) {
         // two columns of the row are left out: one range test per 16 bytes, and the per-element selects only in the vector that holds one
         if ((unsigned)(blank - v0) < (unsigned)NV || (unsigned)(yv - v0) < (unsigned)NV) {
 #pragma unroll
             for (int k = 0; k < NV; ++k) x.f[k] = other(x.f[k], v0 + k);
         }
-        float mx = x.f[0];
-#pragma unroll
-        for (int k = 1; k < NV; ++k) mx = fmaxf(mx, x.f[k]);
-        const float mn = fmaxf(m, mx);
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) acc += __expf(x.f[k] - mn);
-        s = s * __expf(m - mn) + acc;
-        m = mn;
-    }
-    for (int i = head + nvec * NV + lane; i < V; i += 64) upd(other(ldf<TL>(r + i), i));
-    const float M = wave_max(m);
-    s = wave_sum(s * __expf(m - M));
+    });
     if (lane == 0) {
         const float lo_raw = M + __logf(s);                    // -inf when no other column carries mass (V = 2, or all of them -inf)
         const float zb = ldf<TL>(r + blank);
@@ -151,16 +125,13 @@ __global__ __launch_bounds__(KD_WAVES * 64) void kd_grad_kernel(
     const TL* logits, long ldv, const int* __restrict__ labels, const int* __restrict__ act_lens, const int* __restrict__ label_lens,
     int B, int T, int U1, int V, int blank, int vec_ok, const float4* __restrict__ rec, const float* __restrict__ grad_out,
     int grad_out_stride, float scale, TL* grad, long ldg) {
-    constexpr int NV = 16 / sizeof(TL);
+    constexpr int NV = Vec16<TL>::NV;
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * KD_WAVES + (threadIdx.x >> 6);
     if (row >= (long)B * T * U1) return;
-    const int u = (int)(row % U1);
-    const long bt = row / U1;
-    const int t = (int)(bt % T);
-    const int b = (int)(bt / T);
-    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U1 - 1);
-    const bool valid = (t < Tb) && (u <= Ub);
+    const LatticeRow p = lattice_row(row, T, U1, act_lens, label_lens);
+    const int b = p.b, u = p.u, Ub = p.Ub;
+    const bool valid = p.inside();
     if (ACC && !valid) return;             // accumulate: nothing outside the lattice's rows is touched
     const TL* r = logits + row * ldv;
     TL* g = grad + row * ldg;
@@ -186,9 +157,10 @@ __global__ __launch_bounds__(KD_WAVES * 64) void kd_grad_kernel(
     // f for a vector that holds neither the blank nor the label column (one range test per 16 bytes): the same arithmetic, no selects
     auto fo = [&](float x) -> float { return valid ? gs * (__expf(x - l) * ko) : 0.f; };
     auto special = [&](int v0) -> bool { return (unsigned)(blank - v0) < (unsigned)NV || (unsigned)(yv - v0) < (unsigned)NV; };
-    const int head = row_head<TL>(r, V, vec_ok);
-    const int nvec = (V - head) / NV;
     if constexpr (ACC) {
+        // the one read-modify-write walk, and the one that must leave the pad columns [V, ldg) alone: not a row_map
+        const int head = row_head<TL>(r, V, vec_ok);
+        const int nvec = (V - head) / NV;
         for (int i = lane; i < head; i += 64) stf<TL>(g + i, ldf<TL>(g + i) + f(ldf<TL>(r + i), i));
         for (int i = lane; i < nvec; i += 64) {
             Vec16<TL> x, a;
@@ -207,23 +179,15 @@ __global__ __launch_bounds__(KD_WAVES * 64) void kd_grad_kernel(
         for (int i = head + nvec * NV + lane; i < V; i += 64) stf<TL>(g + i, ldf<TL>(g + i) + f(ldf<TL>(r + i), i));
     } else {
         // in place: every lane overwrites only the elements it has read itself, and the row's record lives in the workspace
-        for (int i = lane; i < head; i += 64) stf<TL>(g + i, f(valid ? ldf<TL>(r + i) : 0.f, i));
-        for (int i = lane; i < nvec; i += 64) {
-            Vec16<TL> x;
-            const int v0 = head + i * NV;
-            if (valid) x.load(r + v0);
+        row_map<TL>(r, g, V, ldg, vec_ok, lane, valid, f, [&](Vec16<TL>& x, int v0) {
             if (special(v0)) {
 #pragma unroll
-                for (int k = 0; k < NV; ++k) x.f[k] = f(valid ? x.f[k] : 0.f, v0 + k);
+                for (int k = 0; k < NV; ++k) x.f[k] = f(x.f[k], v0 + k);
             } else {
 #pragma unroll
-                for (int k = 0; k < NV; ++k) x.f[k] = fo(valid ? x.f[k] : 0.f);
+                for (int k = 0; k < NV; ++k) x.f[k] = fo(x.f[k]);
             }
-            x.store(g + v0);
-        }
-        for (int i = head + nvec * NV + lane; i < V; i += 64) stf<TL>(g + i, f(valid ? ldf<TL>(r + i) : 0.f, i));
-        // padded pitch: columns [V, ldg) are zeroed so that the joint's dgrad GEMM may run over the full pitch
-        for (int i = V + lane; i < ldg; i += 64) stf<TL>(g + i, 0.f);
+        });
     }
 }
 
@@ -231,7 +195,7 @@ template <typename TL, bool TEACHER>
 void kd_launch_rows(hipStream_t st, const void* logits, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T,
                     int U1, int V, int blank, const float* teacher, float* post, float4* rec, float* cost) {
     const long rows = (long)B * T * U1;
-    const int vec_ok = ((reinterpret_cast<uintptr_t>(logits) % sizeof(TL)) == 0) ? 1 : 0;
+    const int vec_ok = rows_vec_ok(logits, sizeof(TL));
     hipLaunchKernelGGL((kd_row_kernel<TL, TEACHER>), dim3(cdiv(rows, KD_WAVES)), dim3(KD_WAVES * 64), 0, st, static_cast<const TL*>(logits), ldv,
                        labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok, teacher, post, rec, cost);
 }
@@ -240,10 +204,7 @@ template <typename TL, bool ACC>
 void kd_launch_grad(hipStream_t st, const void* logits, long ldv, const int* labels, const int* act_lens, const int* label_lens, int B, int T,
                     int U1, int V, int blank, const float4* rec, const float* grad_out, int grad_out_stride, float scale, void* grad, long ldg) {
     const long rows = (long)B * T * U1;
-    const long es = (long)sizeof(TL);
-    // vector path needs logits and grad rows to share their 16-byte phase
-    const int vec_ok = ((reinterpret_cast<uintptr_t>(logits) % 16) == (reinterpret_cast<uintptr_t>(grad) % 16) && ((ldv - ldg) * es) % 16 == 0 &&
-                        (reinterpret_cast<uintptr_t>(logits) % es) == 0) ? 1 : 0;
+    const int vec_ok = rows_vec_ok(logits, grad, ldv, ldg, sizeof(TL));
     hipLaunchKernelGGL((kd_grad_kernel<TL, ACC>), dim3(cdiv(rows, KD_WAVES)), dim3(KD_WAVES * 64), 0, st, static_cast<const TL*>(logits), ldv,
                        labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok, rec, grad_out, grad_out_stride, scale, static_cast<TL*>(grad), ldg);
 }
@@ -270,10 +231,9 @@ int ttmi_kd_collapse(const void* logits, int dtype, long ldv, const int* labels,
     TTMI_REQUIRE(logits && (labels || U1 == 1) && act_lens && label_lens && post, "kd_collapse: null pointer");
     KD_CHECK_COMMON("kd_collapse");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (dtype == 0)
-        kd_launch_rows<float, false>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, nullptr, post, nullptr, nullptr);
-    else
-        kd_launch_rows<bf16_t, false>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, nullptr, post, nullptr, nullptr);
+    by_dtype(dtype, [&](auto z) {
+        kd_launch_rows<decltype(z), false>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, nullptr, post, nullptr, nullptr);
+    });
     TTMI_LAUNCH_CHECK("kd_row_kernel");
     return TTMI_OK;
 }
@@ -285,10 +245,9 @@ int ttmi_kd_loss_fwd(const void* logits, int dtype, long ldv, const int* labels,
     TTMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "kd_loss_fwd: workspace must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const KdWs w = kd_carve(workspace, B, T, U1);
-    if (dtype == 0)
-        kd_launch_rows<float, true>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, teacher, nullptr, w.rec, w.cost);
-    else
-        kd_launch_rows<bf16_t, true>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, teacher, nullptr, w.rec, w.cost);
+    by_dtype(dtype, [&](auto z) {
+        kd_launch_rows<decltype(z), true>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, teacher, nullptr, w.rec, w.cost);
+    });
     TTMI_LAUNCH_CHECK("kd_row_kernel");
     hipLaunchKernelGGL(kd_sum_kernel, dim3(B), dim3(KD_SUM_THREADS), 0, st, w.cost, act_lens, label_lens, T, U1, costs);
     TTMI_LAUNCH_CHECK("kd_sum_kernel");
@@ -307,14 +266,13 @@ int ttmi_kd_loss_bwd(const void* logits, int dtype, long ldv, const int* labels,
     TTMI_REQUIRE(logits != static_cast<const void*>(grad) || !accumulate, "kd_loss_bwd: accumulate = 1 cannot add to the logits themselves");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const KdWs w = kd_carve(const_cast<void*>(workspace), B, T, U1);
-    if (dtype == 0 && !accumulate)
-        kd_launch_grad<float, false>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, w.rec, grad_out, grad_out_stride, scale, grad, ldg);
-    else if (dtype == 0)
-        kd_launch_grad<float, true>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, w.rec, grad_out, grad_out_stride, scale, grad, ldg);
-    else if (!accumulate)
-        kd_launch_grad<bf16_t, false>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, w.rec, grad_out, grad_out_stride, scale, grad, ldg);
-    else
-        kd_launch_grad<bf16_t, true>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, w.rec, grad_out, grad_out_stride, scale, grad, ldg);
+    by_dtype(dtype, [&](auto z) {
+        using TL = decltype(z);
+        if (accumulate)
+            kd_launch_grad<TL, true>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, w.rec, grad_out, grad_out_stride, scale, grad, ldg);
+        else
+            kd_launch_grad<TL, false>(st, logits, ldv, labels, act_lens, label_lens, B, T, U1, V, blank, w.rec, grad_out, grad_out_stride, scale, grad, ldg);
+    });
     TTMI_LAUNCH_CHECK("kd_grad_kernel");
     return TTMI_OK;
 }

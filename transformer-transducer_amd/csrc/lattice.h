@@ -1,7 +1,15 @@
-// Pieces shared by the lattice losses (rnnt.hip, ctc.hip): the fp64 frontier and its log-add-exp, the one-lane DPP wave rotates, and the
-// 16-byte row walk over f32 / bf16 logits rows of any alignment.
+// Pieces shared by the lattice losses (rnnt.hip, mono.hip, ctc.hip, distill.hip):
+//   * the fp64 frontier and its log-add-exp, the one-lane DPP wave rotates;
+//   * the 16-byte access to f32 / bf16 logits rows of any alignment (Vec16, ldf / stf, row_head) and the two walks of one row by one wave
+//     built on it: row_lse (online log-sum-exp) and row_map (gradient: g[v] = f(r[v], v), pad columns zeroed).  The kernels keep their own
+//     row terms, their lambdas and their lane-0 epilogues; what differs between the losses on purpose stays in them;
+//   * lattice_row: row -> (b, t, u) and the utterance's clamped lengths;
+//   * host side: rows_vec_ok (when the walks may use 16-byte accesses), by_dtype (one call site for the f32 / bf16 instantiations),
+//     with_slots (the slots-per-lane / prefetch-depth ladder of the one-wave lattice walks) and launch_dec_lds (forced alignment: decision
+//     words in LDS when they fit, else in the caller's workspace).
 #pragma once
 #include "common.h"
+#include <type_traits>
 
 namespace ttmi_lattice {
 
@@ -84,6 +92,147 @@ __device__ __forceinline__ int row_head(const TL* r, int V, int vec_ok) {
     constexpr int NV = 16 / sizeof(TL);
     int head = vec_ok ? (int)((NV - ((reinterpret_cast<uintptr_t>(r) / sizeof(TL)) % NV)) % NV) : V;
     return head > V ? V : head;
+}
+
+
+// ------------------------------------------------------------------ one row, one wave: online log-sum-exp
+// Scalar head up to the first 16-byte boundary, 16-byte vectors (one running-max update per vector), scalar tail, then the wave's max M and
+// S = sum exp(x - M): the row's log-sum-exp is M + log S.  el(x, v) maps a head / tail element of column v, vec(x, v0) may edit the vector
+// of columns v0 .. v0 + NV - 1 before it is summed.  Plain loads: see the timings in Vec16::load.
+template <typename TL, typename El, typename Vec>
+__device__ __forceinline__ void row_lse(const TL* __restrict__ r, int V, int vec_ok, int lane, float& M, float& S, El&& el, Vec&& vec) {
+    constexpr int NV = Vec16<TL>::NV;
+    float m = NEG, s = 0.f;
+    auto upd = [&](float x) {
+        const float mn = fmaxf(m, x);
+        s = s * __expf(m - mn) + __expf(x - mn);
+        m = mn;
+    };
+    const int head = row_head<TL>(r, V, vec_ok);
+    for (int i = lane; i < head; i += 64) upd(el(ldf<TL>(r + i), i));
+    const int nvec = (V - head) / NV;
+    for (int i = lane; i < nvec; i += 64) {
+        Vec16<TL> x;
+        const int v0 = head + i * NV;
+        x.template load<false>(r + v0);
+        vec(x, v0);
+        float mx = x.f[0];
+#pragma unroll
+        for (int k = 1; k < NV; ++k) mx = fmaxf(mx, x.f[k]);
+        const float mn = fmaxf(m, mx);
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) acc += __expf(x.f[k] - mn);
+        s = s * __expf(m - mn) + acc;
+        m = mn;
+    }
+    for (int i = head + nvec * NV + lane; i < V; i += 64) upd(el(ldf<TL>(r + i), i));
+    M = wave_max(m);
+    S = wave_sum(s * __expf(m - M));
+}
+template <typename TL>
+__device__ __forceinline__ void row_lse(const TL* __restrict__ r, int V, int vec_ok, int lane, float& M, float& S) {
+    row_lse<TL>(r, V, vec_ok, lane, M, S, [](float x, int) { return x; }, [](Vec16<TL>&, int) {});
+}
+
+// ------------------------------------------------------------------ one row, one wave: gradient
+// g[v] = f(valid ? r[v] : 0, v) for v < V and g[v] = 0 for the pad columns [V, ldg), which the dgrad GEMMs run over.  A row that is not
+// valid is not read.  g may be r (in place): every lane overwrites only the elements it has read itself - a caller whose row terms read
+// r[...] puts a wave barrier between those reads and this walk.  fvec(x, v0) maps a whole vector (columns v0 .. v0 + NV - 1) in place.
+template <typename TL, typename F, typename FV>
+__device__ __forceinline__ void row_map(const TL* r, TL* g, int V, long ldg, int vec_ok, int lane, bool valid, F&& f, FV&& fvec) {
+    constexpr int NV = Vec16<TL>::NV;
+    const int head = row_head<TL>(r, V, vec_ok);
+    for (int i = lane; i < head; i += 64) stf<TL>(g + i, f(valid ? ldf<TL>(r + i) : 0.f, i));
+    const int nvec = (V - head) / NV;
+    for (int i = lane; i < nvec; i += 64) {
+        Vec16<TL> x;
+        const int v0 = head + i * NV;
+        if (valid) x.load(r + v0);
+#pragma unroll
+        for (int k = 0; k < NV; ++k) x.f[k] = valid ? x.f[k] : 0.f;
+        fvec(x, v0);
+        x.store(g + v0);
+    }
+    for (int i = head + nvec * NV + lane; i < V; i += 64) stf<TL>(g + i, f(valid ? ldf<TL>(r + i) : 0.f, i));
+    for (int i = V + lane; i < ldg; i += 64) stf<TL>(g + i, 0.f);
+}
+template <typename TL, typename F>
+__device__ __forceinline__ void row_map(const TL* r, TL* g, int V, long ldg, int vec_ok, int lane, bool valid, F&& f) {
+    row_map<TL>(r, g, V, ldg, vec_ok, lane, valid, f, [&](Vec16<TL>& x, int v0) {
+#pragma unroll
+        for (int k = 0; k < Vec16<TL>::NV; ++k) x.f[k] = f(x.f[k], v0 + k);
+    });
+}
+
+// ------------------------------------------------------------------ row -> lattice node
+struct LatticeRow {
+    int b, t, u;      // row = (b * T + t) * U1 + u
+    int Tb, Ub;       // the utterance's frames and labels, clamped into the padded lattice
+    __device__ __forceinline__ bool inside() const { return t < Tb && u <= Ub; }
+};
+__device__ __forceinline__ LatticeRow lattice_row(long row, int T, int U1, const int* __restrict__ act_lens, const int* __restrict__ label_lens) {
+    LatticeRow p;
+    p.u = (int)(row % U1);
+    const long bt = row / U1;
+    p.t = (int)(bt % T);
+    p.b = (int)(bt / T);
+    p.Tb = clampi(act_lens[p.b], 1, T);
+    p.Ub = clampi(label_lens[p.b], 0, U1 - 1);
+    return p;
+}
+
+// ------------------------------------------------------------------ host side
+// read-only walk: vectors whenever the elements themselves are aligned (row_head finds each row's first 16-byte boundary)
+inline int rows_vec_ok(const void* logits, size_t es) { return (reinterpret_cast<uintptr_t>(logits) % es) == 0 ? 1 : 0; }
+// gradient walk: logits and grad rows must also share their 16-byte phase
+inline int rows_vec_ok(const void* logits, const void* grad, long ldv, long ldg, size_t es) {
+    return ((reinterpret_cast<uintptr_t>(logits) % 16) == (reinterpret_cast<uintptr_t>(grad) % 16) && ((ldv - ldg) * (long)es) % 16 == 0 &&
+            rows_vec_ok(logits, es)) ? 1 : 0;
+}
+
+// fn(TL{}) with TL = float (dtype 0) or bf16_t (dtype 1): `using TL = decltype(z)` names the row kernel's instantiation
+template <typename Fn>
+void by_dtype(int dtype, Fn&& fn) {
+    if (dtype == 0) fn(float{});
+    else fn(bf16_t{});
+}
+
+// the one-wave lattice walks: lane l, slot r owns label u = 64 r + l.  fn(R, PF) with R = slots per lane (64 R >= U1 <= 1024) and
+// PF = emission rows per prefetch chunk (shrinks as R grows, to stay in registers), both std::integral_constant
+template <typename Fn>
+auto with_slots(int U1, Fn&& fn) {
+    using std::integral_constant;
+    if (U1 <= 64) return fn(integral_constant<int, 1>{}, integral_constant<int, 8>{});
+    if (U1 <= 128) return fn(integral_constant<int, 2>{}, integral_constant<int, 8>{});
+    if (U1 <= 256) return fn(integral_constant<int, 4>{}, integral_constant<int, 4>{});
+    if (U1 <= 512) return fn(integral_constant<int, 8>{}, integral_constant<int, 2>{});
+    return fn(integral_constant<int, 16>{}, integral_constant<int, 1>{});
+}
+
+// Forced alignment keeps one utterance's decision words in dynamic LDS (k_lds, `bytes` of it) up to VIT_LDS_MAX, else in the caller's
+// workspace (k_ws).  debug = ttmi_set_option(23, bits): 1 = the workspace whatever the shape, 2 = no backtrace (measurements / tests);
+// `backtrace` is the kernels' last argument.
+constexpr size_t VIT_LDS_MAX = 128 * 1024;      // of the CU's 160 KB
+template <typename... KArgs, typename... Args>
+int launch_dec_lds(const char* what, void (*k_lds)(KArgs...), void (*k_ws)(KArgs...), size_t bytes, int debug, dim3 grid, dim3 block,
+                   hipStream_t st, Args... args) {
+    const int backtrace = (debug & 2) ? 0 : 1;
+    if (bytes <= VIT_LDS_MAX && !(debug & 1)) {
+        if (bytes > 64 * 1024) {
+            // above the default limit the attribute is needed, and it belongs to the current DEVICE: it is set on every such call (a host-side
+            // call, no stream work) instead of being remembered per process
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)VIT_LDS_MAX);
+            if (e != hipSuccess) {
+                ttmi_set_error("%s: cannot reserve %zu bytes of LDS: %s", what, bytes, hipGetErrorString(e));
+                return (int)e;
+            }
+        }
+        hipLaunchKernelGGL(k_lds, grid, block, bytes, st, args..., backtrace);
+    } else {
+        hipLaunchKernelGGL(k_ws, grid, block, 0, st, args..., backtrace);
+    }
+    return TTMI_OK;
 }
 
 }  // namespace ttmi_lattice

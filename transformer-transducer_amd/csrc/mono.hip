@@ -2,7 +2,7 @@
 // exactly ONE decision, blank or one label, and the emitting frame is consumed (include/ttmi.h has the recursion).  No reference
 // counterpart: the reference trains the standard lattice alone (rnnt.hip), which this file leaves untouched.
 //
-//   mono_lse_kernel        HBM-bound: one wave per (b,t,u) row of V logits, the 16-byte online log-sum-exp walk of rnnt_lse_kernel; emits lse
+//   mono_lse_kernel        HBM-bound: one wave per (b,t,u) row of V logits, lattice.h's row_lse walk (shared with rnnt_lse_kernel); emits lse
 //                          and the row's two emission log-probs TIME-MAJOR ([b][t][u]): the recursion is frame-synchronous and reads one
 //                          whole frame row per step (rnnt.hip's diagonal-major layout serves its anti-diagonal frontier, not this one).
 //   mono_alphabeta_kernel  latency-bound dynamic programme: one wave per (utterance, direction), T_b serial steps (the standard lattice
@@ -47,42 +47,15 @@ __global__ __launch_bounds__(MONO_WAVES * 64) void mono_lse_kernel(
     const TL* __restrict__ logits, long ldv, const int* __restrict__ labels, const int* __restrict__ act_lens,
     const int* __restrict__ label_lens, int B, int T, int U1, int V, int blank, int vec_ok, float* __restrict__ lse,
     float* __restrict__ lpb, float* __restrict__ lpl) {
-    constexpr int NV = 16 / sizeof(TL);
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * MONO_WAVES + (threadIdx.x >> 6);
     if (row >= (long)B * T * U1) return;
-    const int u = (int)(row % U1);
-    const long bt = row / U1;
-    const int t = (int)(bt % T);
-    const int b = (int)(bt / T);
-    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U1 - 1);
-    if (t >= Tb || u > Ub) return;         // (the lattice walk and the gradient never read these entries)
+    const LatticeRow p = lattice_row(row, T, U1, act_lens, label_lens);
+    if (!p.inside()) return;               // (the lattice walk and the gradient never read these entries)
+    const int b = p.b, u = p.u, Ub = p.Ub;
     const TL* r = logits + row * ldv;
-    float m = NEG, s = 0.f;
-    auto upd = [&](float x) {
-        const float mn = fmaxf(m, x);
-        s = s * __expf(m - mn) + __expf(x - mn);
-        m = mn;
-    };
-    const int head = row_head<TL>(r, V, vec_ok);
-    for (int i = lane; i < head; i += 64) upd(ldf<TL>(r + i));
-    const int nvec = (V - head) / NV;
-    for (int i = lane; i < nvec; i += 64) {
-        Vec16<TL> x;
-        x.template load<false>(r + head + i * NV);
-        float mx = x.f[0];
-#pragma unroll
-        for (int k = 1; k < NV; ++k) mx = fmaxf(mx, x.f[k]);
-        const float mn = fmaxf(m, mx);
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) acc += __expf(x.f[k] - mn);
-        s = s * __expf(m - mn) + acc;
-        m = mn;
-    }
-    for (int i = head + nvec * NV + lane; i < V; i += 64) upd(ldf<TL>(r + i));
-    const float M = wave_max(m);
-    s = wave_sum(s * __expf(m - M));
+    float M, s;
+    row_lse<TL>(r, V, vec_ok, lane, M, s);
     if (lane == 0) {
         const float l = M + __logf(s);
         lse[row] = l;
@@ -217,13 +190,6 @@ __global__ __launch_bounds__(64) void mono_alphabeta_kernel(const float* __restr
     }
 }
 
-template <int R, int PF>
-void mono_launch_alphabeta(hipStream_t st, int B, const MonoWs& w, const int* act_lens, const int* label_lens, int T, int U1,
-                           float* costs) {
-    hipLaunchKernelGGL((mono_alphabeta_kernel<R, PF>), dim3(2 * B), dim3(64), 0, st, w.lpb, w.lpl, act_lens, label_lens, T, U1, w.alpha,
-                       w.beta, w.ll, costs);
-}
-
 // ------------------------------------------------------------------ gradient
 template <typename TL>
 __global__ __launch_bounds__(MONO_WAVES * 64) void mono_grad_kernel(
@@ -231,20 +197,15 @@ __global__ __launch_bounds__(MONO_WAVES * 64) void mono_grad_kernel(
     int B, int T, int U1, int V, int blank, int vec_ok, const float* __restrict__ lse, const acc_t* __restrict__ alpha_g,
     const acc_t* __restrict__ beta_g, const acc_t* __restrict__ ll, const float* __restrict__ grad_out, int grad_out_stride, float scale,
     TL* grad, long ldg) {
-    constexpr int NV = 16 / sizeof(TL);
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * MONO_WAVES + (threadIdx.x >> 6);
     if (row >= (long)B * T * U1) return;
-    const int u = (int)(row % U1);
-    const long bt = row / U1;
-    const int t = (int)(bt % T);
-    const int b = (int)(bt / T);
-    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U1 - 1);
+    const LatticeRow p = lattice_row(row, T, U1, act_lens, label_lens);
+    const int b = p.b, t = p.t, u = p.u, Ub = p.Ub;
     const acc_t L = ll[b];
     // rows outside the lattice and utterances without a path (U_b > T_b): zero rows
-    const bool valid = (t < Tb) && (u <= Ub) && !(L <= MONO_DEAD);
+    const bool valid = p.inside() && !(L <= MONO_DEAD);
     const TL* r = logits + row * ldv;
-    TL* g = grad + row * ldg;
     float c = 0.f, eb = 0.f, el = 0.f, gs = 0.f;
     int yv = -1;
     if (valid) {
@@ -263,26 +224,12 @@ __global__ __launch_bounds__(MONO_WAVES * 64) void mono_grad_kernel(
     }
     // every lane has read r[blank], r[yv] before any lane overwrites them (in-place use)
     __builtin_amdgcn_wave_barrier();
-    auto f = [&](float x, int v) -> float {
+    row_map<TL>(r, grad + row * ldg, V, ldg, vec_ok, lane, valid, [&](float x, int v) -> float {
         float e = __expf(x + c);
         e -= (v == blank) ? eb : 0.f;
         e -= (v == yv) ? el : 0.f;
         return valid ? gs * e : 0.f;
-    };
-    const int head = row_head<TL>(r, V, vec_ok);
-    for (int i = lane; i < head; i += 64) stf<TL>(g + i, f(valid ? ldf<TL>(r + i) : 0.f, i));
-    const int nvec = (V - head) / NV;
-    for (int i = lane; i < nvec; i += 64) {
-        Vec16<TL> x;
-        const int v0 = head + i * NV;
-        if (valid) x.load(r + v0);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) x.f[k] = f(valid ? x.f[k] : 0.f, v0 + k);
-        x.store(g + v0);
-    }
-    for (int i = head + nvec * NV + lane; i < V; i += 64) stf<TL>(g + i, f(valid ? ldf<TL>(r + i) : 0.f, i));
-    // padded pitch: columns [V, ldg) are zeroed so that the joint's dgrad GEMM may run over the full pitch
-    for (int i = V + lane; i < ldg; i += 64) stf<TL>(g + i, 0.f);
+    });
 }
 
 // ------------------------------------------------------------------ forced alignment: best path through the monotonic lattice
@@ -435,31 +382,7 @@ __global__ __launch_bounds__(MONO_ES_WAVES * 64) void mono_emit_stats_kernel(
     }
 }
 
-constexpr size_t MONO_VIT_LDS_MAX = 128 * 1024;      // rnnt.hip's VIT_LDS_MAX: decision words of one utterance kept in LDS up to here (of the CU's 160 KB)
 __host__ __device__ __forceinline__ size_t mono_dec_bytes(int T, int U1) { return (size_t)T * ((U1 + 63) / 64) * sizeof(dec_t); }
-
-template <int R, int PF>
-int mono_launch_viterbi(hipStream_t st, int B, const MonoWs& w, const int* al, const int* ll_, int T, int U1, dec_t* dec_ws, int* frames,
-                        float* score, int debug) {
-    const int W = (U1 + 63) / 64;
-    const size_t lds = mono_dec_bytes(T, U1);
-    const int backtrace = (debug & 2) ? 0 : 1;
-    if (lds <= MONO_VIT_LDS_MAX && !(debug & 1)) {
-        if (lds > 64 * 1024) {
-            // above the default limit the attribute is needed, and it belongs to the current DEVICE: it is set on every such call (a host-side
-            // call, no stream work) instead of being remembered per process
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mono_viterbi_kernel<R, PF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MONO_VIT_LDS_MAX);
-            if (e != hipSuccess) {
-                ttmi_set_error("mono align: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-                return (int)e;
-            }
-        }
-        hipLaunchKernelGGL((mono_viterbi_kernel<R, PF, true>), dim3(B), dim3(64), lds, st, w.lpb, w.lpl, al, ll_, T, U1, W, dec_ws, frames, score, backtrace);
-    } else {
-        hipLaunchKernelGGL((mono_viterbi_kernel<R, PF, false>), dim3(B), dim3(64), 0, st, w.lpb, w.lpl, al, ll_, T, U1, W, dec_ws, frames, score, backtrace);
-    }
-    return TTMI_OK;
-}
 
 }  // namespace
 
@@ -484,13 +407,11 @@ int ttmi_mono_align(const void* workspace, const int* act_lens, const int* label
     hipStream_t st = static_cast<hipStream_t>(stream);
     const MonoWs w = mono_carve(const_cast<void*>(workspace), B, T, U1);
     dec_t* dec = static_cast<dec_t*>(align_workspace);
-    const int debug = ttmi_rnnt_get_align_debug();
-    int rc;
-    if (U1 <= 64) rc = mono_launch_viterbi<1, 8>(st, B, w, act_lens, label_lens, T, U1, dec, frames, score, debug);
-    else if (U1 <= 128) rc = mono_launch_viterbi<2, 8>(st, B, w, act_lens, label_lens, T, U1, dec, frames, score, debug);
-    else if (U1 <= 256) rc = mono_launch_viterbi<4, 4>(st, B, w, act_lens, label_lens, T, U1, dec, frames, score, debug);
-    else if (U1 <= 512) rc = mono_launch_viterbi<8, 2>(st, B, w, act_lens, label_lens, T, U1, dec, frames, score, debug);
-    else rc = mono_launch_viterbi<16, 1>(st, B, w, act_lens, label_lens, T, U1, dec, frames, score, debug);
+    const int rc = with_slots(U1, [&](auto R, auto PF) {
+        return launch_dec_lds("mono align", mono_viterbi_kernel<R, PF, true>, mono_viterbi_kernel<R, PF, false>, mono_dec_bytes(T, U1),
+                              ttmi_rnnt_get_align_debug(), dim3(B), dim3(64), st, w.lpb, w.lpl, act_lens, label_lens, T, U1, (U1 + 63) / 64,
+                              dec, frames, score);
+    });
     if (rc) return rc;
     TTMI_LAUNCH_CHECK("mono_viterbi_kernel");
     return TTMI_OK;
@@ -528,22 +449,17 @@ int ttmi_mono_loss_fwd(const void* logits, int dtype, long ldv, const int* label
     hipStream_t st = static_cast<hipStream_t>(stream);
     const MonoWs w = mono_carve(workspace, B, T, U1);
     const long rows = (long)B * T * U1;
-    const size_t es = dtype == 0 ? 4 : 2;
-    const int vec_ok = ((reinterpret_cast<uintptr_t>(logits) % es) == 0) ? 1 : 0;
-    if (dtype == 0)
-        hipLaunchKernelGGL(mono_lse_kernel<float>, dim3(cdiv(rows, MONO_WAVES)), dim3(MONO_WAVES * 64), 0, st,
-                           static_cast<const float*>(logits), ldv, labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok, w.lse, w.lpb,
-                           w.lpl);
-    else
-        hipLaunchKernelGGL(mono_lse_kernel<bf16_t>, dim3(cdiv(rows, MONO_WAVES)), dim3(MONO_WAVES * 64), 0, st,
-                           static_cast<const bf16_t*>(logits), ldv, labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok, w.lse, w.lpb,
-                           w.lpl);
+    const int vec_ok = rows_vec_ok(logits, dtype == 0 ? 4 : 2);
+    by_dtype(dtype, [&](auto z) {
+        using TL = decltype(z);
+        hipLaunchKernelGGL(mono_lse_kernel<TL>, dim3(cdiv(rows, MONO_WAVES)), dim3(MONO_WAVES * 64), 0, st, static_cast<const TL*>(logits), ldv,
+                           labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok, w.lse, w.lpb, w.lpl);
+    });
     TTMI_LAUNCH_CHECK("mono_lse_kernel");
-    if (U1 <= 64) mono_launch_alphabeta<1, 8>(st, B, w, act_lens, label_lens, T, U1, costs);
-    else if (U1 <= 128) mono_launch_alphabeta<2, 8>(st, B, w, act_lens, label_lens, T, U1, costs);
-    else if (U1 <= 256) mono_launch_alphabeta<4, 4>(st, B, w, act_lens, label_lens, T, U1, costs);
-    else if (U1 <= 512) mono_launch_alphabeta<8, 2>(st, B, w, act_lens, label_lens, T, U1, costs);
-    else mono_launch_alphabeta<16, 1>(st, B, w, act_lens, label_lens, T, U1, costs);
+    with_slots(U1, [&](auto R, auto PF) {
+        hipLaunchKernelGGL((mono_alphabeta_kernel<R, PF>), dim3(2 * B), dim3(64), 0, st, w.lpb, w.lpl, act_lens, label_lens, T, U1, w.alpha,
+                           w.beta, w.ll, costs);
+    });
     TTMI_LAUNCH_CHECK("mono_alphabeta_kernel");
     return TTMI_OK;
 }
@@ -561,18 +477,13 @@ int ttmi_mono_loss_bwd(const void* logits, int dtype, long ldv, const int* label
     hipStream_t st = static_cast<hipStream_t>(stream);
     const MonoWs w = mono_carve(const_cast<void*>(workspace), B, T, U1);
     const long rows = (long)B * T * U1;
-    const size_t es = dtype == 0 ? 4 : 2;
-    // vector path needs logits and grad rows to share their 16-byte phase
-    const int vec_ok = ((reinterpret_cast<uintptr_t>(logits) % 16) == (reinterpret_cast<uintptr_t>(grad) % 16) &&
-                        ((ldv - ldg) * (long)es) % 16 == 0 && (reinterpret_cast<uintptr_t>(logits) % es) == 0) ? 1 : 0;
-    if (dtype == 0)
-        hipLaunchKernelGGL(mono_grad_kernel<float>, dim3(cdiv(rows, MONO_WAVES)), dim3(MONO_WAVES * 64), 0, st,
-                           static_cast<const float*>(logits), ldv, labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok, w.lse, w.alpha,
-                           w.beta, w.ll, grad_out, grad_out_stride, scale, static_cast<float*>(grad), ldg);
-    else
-        hipLaunchKernelGGL(mono_grad_kernel<bf16_t>, dim3(cdiv(rows, MONO_WAVES)), dim3(MONO_WAVES * 64), 0, st,
-                           static_cast<const bf16_t*>(logits), ldv, labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok, w.lse, w.alpha,
-                           w.beta, w.ll, grad_out, grad_out_stride, scale, static_cast<bf16_t*>(grad), ldg);
+    const int vec_ok = rows_vec_ok(logits, grad, ldv, ldg, dtype == 0 ? 4 : 2);
+    by_dtype(dtype, [&](auto z) {
+        using TL = decltype(z);
+        hipLaunchKernelGGL(mono_grad_kernel<TL>, dim3(cdiv(rows, MONO_WAVES)), dim3(MONO_WAVES * 64), 0, st, static_cast<const TL*>(logits), ldv,
+                           labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok, w.lse, w.alpha, w.beta, w.ll, grad_out, grad_out_stride,
+                           scale, static_cast<TL*>(grad), ldg);
+    });
     TTMI_LAUNCH_CHECK("mono_grad_kernel");
     return TTMI_OK;
 }

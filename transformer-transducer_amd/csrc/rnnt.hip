@@ -38,47 +38,20 @@ __global__ __launch_bounds__(LSE_WAVES * 64) void rnnt_lse_kernel(
     const TL* __restrict__ logits, long ldv, const int* __restrict__ labels, const int* __restrict__ act_lens,
     const int* __restrict__ label_lens, int B, int T, int U1, int V, int blank, int vec_ok,
     float* __restrict__ lse, float* __restrict__ lpb_d, float* __restrict__ lpl_d) {
-    constexpr int NV = 16 / sizeof(TL);
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * LSE_WAVES + (threadIdx.x >> 6);
     if (row >= (long)B * T * U1) return;
-    const int u = (int)(row % U1);
-    const long bt = row / U1;
-    const int t = (int)(bt % T);
-    const int b = (int)(bt / T);
-    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U1 - 1);
-    if (t >= Tb || u > Ub) return;
+    const LatticeRow p = lattice_row(row, T, U1, act_lens, label_lens);
+    if (!p.inside()) return;
+    const int b = p.b, t = p.t, u = p.u, Ub = p.Ub;
     const TL* r = logits + row * ldv;
-    float m = NEG, s = 0.f;
-    auto upd = [&](float x) {
-        const float mn = fmaxf(m, x);
-        s = s * __expf(m - mn) + __expf(x - mn);
-        m = mn;
-    };
-    const int head = row_head<TL>(r, V, vec_ok);
-    for (int i = lane; i < head; i += 64) upd(ldf<TL>(r + i));
-    const int nvec = (V - head) / NV;
-    for (int i = lane; i < nvec; i += 64) {
-        Vec16<TL> x;
-        x.template load<false>(r + head + i * NV);
-        float mx = x.f[0];
-#pragma unroll
-        for (int k = 1; k < NV; ++k) mx = fmaxf(mx, x.f[k]);
-        const float mn = fmaxf(m, mx);
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < NV; ++k) acc += __expf(x.f[k] - mn);
-        s = s * __expf(m - mn) + acc;
-        m = mn;
-    }
-    for (int i = head + nvec * NV + lane; i < V; i += 64) upd(ldf<TL>(r + i));
-    const float M = wave_max(m);
-    s = wave_sum(s * __expf(m - M));
+    float M, s;
+    row_lse<TL>(r, V, vec_ok, lane, M, s);
     if (lane == 0) {
         const float l = M + __logf(s);
         lse[row] = l;
         const long di = (long)b * diag_stride(T, U1) + (long)(t + u) * U1 + u;
-        lpb_d[di] = ldf<TL>(r + blank) - l;
+        lpb_d[di] = ldf<TL>(r + blank) - l;      // not clamped at NEG (mono / ctc / kd clamp theirs)
         float pl = NEG;
         if (u < Ub) {
             int y = labels[(long)b * (U1 - 1) + u];
@@ -471,66 +444,63 @@ __device__ __forceinline__ void fastemit_row(float& c, float& el, float fe, floa
     el *= 1.f + fe;
 }
 
+// A row's gradient is gs * (exp(logit + c) - [blank] eb - [label yv] el): the factors of rnnt_grad_kernel and rnnt_grad_split_kernel.
+// All zero (yv = -1) for a row outside the lattice; r[blank] and r[yv] are read here, before an in-place walk overwrites them.
+struct RnntRowTerms {
+    float c = 0.f, eb = 0.f, el = 0.f, gs = 0.f;
+    int yv = -1;
+};
+template <typename TL>
+__device__ __forceinline__ RnntRowTerms rnnt_row_terms(const LatticeRow& p, long row, const TL* r, const int* __restrict__ labels,
+                                                       int T, int U1, int V, int blank, const float* __restrict__ lse,
+                                                       const acc_t* __restrict__ alpha_d, const acc_t* __restrict__ beta_d,
+                                                       const acc_t* __restrict__ ll, const float* __restrict__ grad_out, int grad_out_stride,
+                                                       float scale, float fe) {
+    RnntRowTerms q;
+    if (p.inside()) {
+        const int b = p.b, t = p.t, u = p.u, Tb = p.Tb, Ub = p.Ub;
+        const acc_t* al = alpha_d + (long)b * diag_stride(T, U1);
+        const acc_t* be = beta_d + (long)b * diag_stride(T, U1);
+        const long di = (long)(t + u) * U1 + u;
+        const float l = lse[row];
+        const acc_t a = al[di] - ll[b * 2];                                     // alpha - ll, fp64
+        q.c = (float)(a + be[di]) - l;
+        q.gs = scale * grad_out[(long)b * grad_out_stride];
+        const float lpb = ldf<TL>(r + blank) - l;
+        if (t == Tb - 1 && u == Ub) q.eb = __expf((float)a + lpb);
+        else if (t < Tb - 1) q.eb = __expf((float)(a + be[di + U1]) + lpb);     // beta[t+1,u]
+        if (u < Ub) {
+            q.yv = clampi(labels[(long)b * (U1 - 1) + u], 0, V - 1);
+            const float lpy = ldf<TL>(r + q.yv) - l;
+            q.el = __expf((float)(a + be[di + U1 + 1]) + lpy);                 // beta[t,u+1]
+            if (fe > 0.f) fastemit_row(q.c, q.el, fe, (float)(be[di + U1 + 1] - be[di]) + lpy);
+        }
+    }
+    return q;
+}
+
 template <typename TL>
 __global__ __launch_bounds__(LSE_WAVES * 64) void rnnt_grad_kernel(
     const TL* logits, long ldv, const int* __restrict__ labels, const int* __restrict__ act_lens,
     const int* __restrict__ label_lens, int B, int T, int U1, int V, int blank, int vec_ok, const float* __restrict__ lse,
     const acc_t* __restrict__ alpha_d, const acc_t* __restrict__ beta_d, const acc_t* __restrict__ ll,
     const float* __restrict__ grad_out, int grad_out_stride, float scale, TL* grad, long ldg, float fe) {
-    constexpr int NV = 16 / sizeof(TL);
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * LSE_WAVES + (threadIdx.x >> 6);
     if (row >= (long)B * T * U1) return;
-    const int u = (int)(row % U1);
-    const long bt = row / U1;
-    const int t = (int)(bt % T);
-    const int b = (int)(bt / T);
-    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U1 - 1);
-    const bool valid = (t < Tb) && (u <= Ub);
+    const LatticeRow p = lattice_row(row, T, U1, act_lens, label_lens);
+    const bool valid = p.inside();
     const TL* r = logits + row * ldv;
-    TL* g = grad + row * ldg;
-    float c = 0.f, eb = 0.f, el = 0.f, gs = 0.f;
-    int yv = -1;
-    if (valid) {
-        const acc_t* al = alpha_d + (long)b * diag_stride(T, U1);
-        const acc_t* be = beta_d + (long)b * diag_stride(T, U1);
-        const long di = (long)(t + u) * U1 + u;
-        const float l = lse[row];
-        const acc_t a = al[di] - ll[b * 2];                                     // alpha - ll, fp64
-        c = (float)(a + be[di]) - l;
-        gs = scale * grad_out[(long)b * grad_out_stride];
-        const float lpb = ldf<TL>(r + blank) - l;
-        if (t == Tb - 1 && u == Ub) eb = __expf((float)a + lpb);
-        else if (t < Tb - 1) eb = __expf((float)(a + be[di + U1]) + lpb);       // beta[t+1,u]
-        if (u < Ub) {
-            yv = clampi(labels[(long)b * (U1 - 1) + u], 0, V - 1);
-            const float lpy = ldf<TL>(r + yv) - l;
-            el = __expf((float)(a + be[di + U1 + 1]) + lpy);                   // beta[t,u+1]
-            if (fe > 0.f) fastemit_row(c, el, fe, (float)(be[di + U1 + 1] - be[di]) + lpy);
-        }
-    }
+    const RnntRowTerms q = rnnt_row_terms<TL>(p, row, r, labels, T, U1, V, blank, lse, alpha_d, beta_d, ll, grad_out, grad_out_stride,
+                                              scale, fe);
     // every lane has read r[blank], r[yv] before any lane overwrites them (in-place use)
     __builtin_amdgcn_wave_barrier();
-    auto f = [&](float x, int v) -> float {
-        float e = __expf(x + c);
-        e -= (v == blank) ? eb : 0.f;
-        e -= (v == yv) ? el : 0.f;
-        return valid ? gs * e : 0.f;
-    };
-    const int head = row_head<TL>(r, V, vec_ok);
-    for (int i = lane; i < head; i += 64) stf<TL>(g + i, f(valid ? ldf<TL>(r + i) : 0.f, i));
-    const int nvec = (V - head) / NV;
-    for (int i = lane; i < nvec; i += 64) {
-        Vec16<TL> x;
-        const int v0 = head + i * NV;
-        if (valid) x.load(r + v0);
-#pragma unroll
-        for (int k = 0; k < NV; ++k) x.f[k] = f(valid ? x.f[k] : 0.f, v0 + k);
-        x.store(g + v0);
-    }
-    for (int i = head + nvec * NV + lane; i < V; i += 64) stf<TL>(g + i, f(valid ? ldf<TL>(r + i) : 0.f, i));
-    // padded pitch: columns [V, ldg) are zeroed so that the joint's dgrad GEMM may run over the full pitch
-    for (int i = V + lane; i < ldg; i += 64) stf<TL>(g + i, 0.f);
+    row_map<TL>(r, grad + row * ldg, V, ldg, vec_ok, lane, valid, [&](float x, int v) -> float {
+        float e = __expf(x + q.c);
+        e -= (v == blank) ? q.eb : 0.f;
+        e -= (v == q.yv) ? q.el : 0.f;
+        return valid ? q.gs * e : 0.f;
+    });
 }
 
 
@@ -547,44 +517,22 @@ __global__ __launch_bounds__(LSE_WAVES * 64) void rnnt_grad_split_kernel(
     const int lane = threadIdx.x & 63;
     const long row = (long)blockIdx.x * LSE_WAVES + (threadIdx.x >> 6);
     if (row >= (long)B * T * U1) return;
-    const int u = (int)(row % U1);
-    const long bt = row / U1;
-    const int t = (int)(bt % T);
-    const int b = (int)(bt / T);
-    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U1 - 1);
-    const bool valid = (t < Tb) && (u <= Ub);
+    const LatticeRow p = lattice_row(row, T, U1, act_lens, label_lens);
+    const bool valid = p.inside();
     float* r = logits + row * ldv;
     const int nvec = (int)(ldv >> 2);
     float4 x[KV];
 #pragma unroll
     for (int k = 0; k < KV; ++k) x[k] = *reinterpret_cast<const float4*>(r + 4 * min(lane + 64 * k, nvec - 1));
-    float c = 0.f, eb = 0.f, el = 0.f, gs = 0.f;
-    int yv = -1;
-    if (valid) {
-        const acc_t* al = alpha_d + (long)b * diag_stride(T, U1);
-        const acc_t* be = beta_d + (long)b * diag_stride(T, U1);
-        const long di = (long)(t + u) * U1 + u;
-        const float l = lse[row];
-        const acc_t a = al[di] - ll[b * 2];
-        c = (float)(a + be[di]) - l;
-        gs = scale * grad_out[(long)b * grad_out_stride];
-        const float lpb = r[blank] - l;
-        if (t == Tb - 1 && u == Ub) eb = __expf((float)a + lpb);
-        else if (t < Tb - 1) eb = __expf((float)(a + be[di + U1]) + lpb);
-        if (u < Ub) {
-            yv = clampi(labels[(long)b * (U1 - 1) + u], 0, V - 1);
-            const float lpy = r[yv] - l;
-            el = __expf((float)(a + be[di + U1 + 1]) + lpy);
-            if (fe > 0.f) fastemit_row(c, el, fe, (float)(be[di + U1 + 1] - be[di]) + lpy);
-        }
-    }
+    const RnntRowTerms q = rnnt_row_terms<float>(p, row, r, labels, T, U1, V, blank, lse, alpha_d, beta_d, ll, grad_out,
+                                                 grad_out_stride, scale, fe);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // the whole row (and r[blank], r[yv]) is in registers before any lane overwrites a byte of it
     __builtin_amdgcn_wave_barrier();
     auto f = [&](float v, int col) -> float {
-        float e = __expf(v + c);
-        e -= (col == blank) ? eb : 0.f;
-        e -= (col == yv) ? el : 0.f;
-        return (valid && col < V) ? gs * e : 0.f;
+        float e = __expf(v + q.c);
+        e -= (col == blank) ? q.eb : 0.f;
+        e -= (col == q.yv) ? q.el : 0.f;
+        return (valid && col < V) ? q.gs * e : 0.f;
     };
     bf16_t* hi = reinterpret_cast<bf16_t*>(r);
     bf16_t* lo = hi + ldv;
@@ -908,38 +856,7 @@ __global__ __launch_bounds__(256) void rnnt_emit_stats_kernel(const acc_t* __res
 }
 
 int g_align_debug = 0;          // ttmi_set_option(23, bits): 1 = decision words in the caller's workspace whatever the shape, 2 = no backtrace (measurements / tests)
-constexpr size_t VIT_LDS_MAX = 128 * 1024;      // decision words of one utterance kept in LDS up to here (of the CU's 160 KB)
 __host__ __device__ __forceinline__ size_t vit_dec_bytes(int T, int U1) { return (size_t)(T + U1 - 1) * ((U1 + 63) / 64) * sizeof(dec_t); }
-
-template <int R, int PF>
-int launch_viterbi(hipStream_t st, int B, const float* lpb, const float* lpl, const int* al, const int* ll_, int T, int U1, dec_t* dec_ws,
-                   int* frames, float* score) {
-    const int W = (U1 + 63) / 64;
-    const size_t lds = vit_dec_bytes(T, U1);
-    const int backtrace = (g_align_debug & 2) ? 0 : 1;
-    if (lds <= VIT_LDS_MAX && !(g_align_debug & 1)) {
-        if (lds > 64 * 1024) {
-            // above the default limit the attribute is needed, and it belongs to the current DEVICE: it is set on every such call (a host-side
-            // call, no stream work) instead of being remembered per process
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(rnnt_viterbi_kernel<R, PF, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)VIT_LDS_MAX);
-            if (e != hipSuccess) {
-                ttmi_set_error("rnnt align: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
-                return (int)e;
-            }
-        }
-        hipLaunchKernelGGL((rnnt_viterbi_kernel<R, PF, true>), dim3(B), dim3(64), lds, st, lpb, lpl, al, ll_, T, U1, W, dec_ws, frames, score, backtrace);
-    } else {
-        hipLaunchKernelGGL((rnnt_viterbi_kernel<R, PF, false>), dim3(B), dim3(64), 0, st, lpb, lpl, al, ll_, T, U1, W, dec_ws, frames, score, backtrace);
-    }
-    return TTMI_OK;
-}
-
-template <int R, int PF>
-void launch_alphabeta(hipStream_t st, int B, const float* lpb, const float* lpl, const int* al, const int* ll_, int T, int U1,
-                      acc_t* a, acc_t* b, acc_t* ll, float* costs) {
-    hipLaunchKernelGGL((rnnt_alphabeta_kernel<R, PF>), dim3(2 * B), dim3(64), 0, st, lpb, lpl, al, ll_, T, U1, a, b, ll, costs);
-}
-
 
 int g_lattice_version = 0;      // ttmi_set_option(9, 1): the round-1 kernel (one wave per utterance and direction) for A/B measurements
 // alpha + beta of B utterances.  Default: rnnt_lattice_lds_kernel (one workgroup per utterance and direction: one wave per 64 labels + a helper
@@ -968,11 +885,9 @@ int launch_lattice(hipStream_t st, int B, const float* lpb, const float* lpl, co
         hipLaunchKernelGGL(rnnt_lattice_lds_kernel, dim3(2 * B), dim3((W + 1) * 64), lds, st, lpb, lpl, al, ll_, T, U1, W, CH, a, b, ll, costs);
         return TTMI_OK;
     }
-    if (U1 <= 64) launch_alphabeta<1, 8>(st, B, lpb, lpl, al, ll_, T, U1, a, b, ll, costs);
-    else if (U1 <= 128) launch_alphabeta<2, 8>(st, B, lpb, lpl, al, ll_, T, U1, a, b, ll, costs);
-    else if (U1 <= 256) launch_alphabeta<4, 4>(st, B, lpb, lpl, al, ll_, T, U1, a, b, ll, costs);
-    else if (U1 <= 512) launch_alphabeta<8, 2>(st, B, lpb, lpl, al, ll_, T, U1, a, b, ll, costs);
-    else launch_alphabeta<16, 1>(st, B, lpb, lpl, al, ll_, T, U1, a, b, ll, costs);
+    with_slots(U1, [&](auto R, auto PF) {
+        hipLaunchKernelGGL((rnnt_alphabeta_kernel<R, PF>), dim3(2 * B), dim3(64), 0, st, lpb, lpl, al, ll_, T, U1, a, b, ll, costs);
+    });
     return TTMI_OK;
 }
 
@@ -1025,17 +940,13 @@ int ttmi_rnnt_loss_fwd(const void* logits, int dtype, long ldv, const int* label
     hipStream_t st = static_cast<hipStream_t>(stream);
     Ws w = carve(workspace, B, T, U1);
     const long rows = (long)B * T * U1;
-    const size_t es = dtype == 0 ? 4 : 2;
-    const int vec_ok = ((reinterpret_cast<uintptr_t>(logits) % es) == 0) ? 1 : 0;
+    const int vec_ok = rows_vec_ok(logits, dtype == 0 ? 4 : 2);
     ttmi_probe_begin(1, st);
-    if (dtype == 0)
-        hipLaunchKernelGGL(rnnt_lse_kernel<float>, dim3(cdiv(rows, LSE_WAVES)), dim3(LSE_WAVES * 64), 0, st,
-                           static_cast<const float*>(logits), ldv, labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok,
-                           w.lse, w.lpb, w.lpl);
-    else
-        hipLaunchKernelGGL(rnnt_lse_kernel<bf16_t>, dim3(cdiv(rows, LSE_WAVES)), dim3(LSE_WAVES * 64), 0, st,
-                           static_cast<const bf16_t*>(logits), ldv, labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok,
-                           w.lse, w.lpb, w.lpl);
+    by_dtype(dtype, [&](auto z) {
+        using TL = decltype(z);
+        hipLaunchKernelGGL(rnnt_lse_kernel<TL>, dim3(cdiv(rows, LSE_WAVES)), dim3(LSE_WAVES * 64), 0, st, static_cast<const TL*>(logits), ldv,
+                           labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok, w.lse, w.lpb, w.lpl);
+    });
     TTMI_LAUNCH_CHECK("rnnt_lse_kernel");
     const int lat_rc = launch_lattice(st, B, w.lpb, w.lpl, act_lens, label_lens, T, U1, w.alpha, w.beta, w.ll, costs);
     ttmi_probe_end(1, st);
@@ -1059,19 +970,14 @@ int ttmi_rnnt_loss_bwd_fe(const void* logits, int dtype, long ldv, const int* la
     hipStream_t st = static_cast<hipStream_t>(stream);
     Ws w = carve(const_cast<void*>(workspace), B, T, U1);
     const long rows = (long)B * T * U1;
-    const size_t es = dtype == 0 ? 4 : 2;
-    // vector path needs logits and grad rows to share their 16-byte phase
-    const int vec_ok = ((reinterpret_cast<uintptr_t>(logits) % 16) == (reinterpret_cast<uintptr_t>(grad) % 16) &&
-                        ((ldv - ldg) * (long)es) % 16 == 0 && (reinterpret_cast<uintptr_t>(logits) % es) == 0) ? 1 : 0;
+    const int vec_ok = rows_vec_ok(logits, grad, ldv, ldg, dtype == 0 ? 4 : 2);
     ttmi_probe_begin(2, st);
-    if (dtype == 0)
-        hipLaunchKernelGGL(rnnt_grad_kernel<float>, dim3(cdiv(rows, LSE_WAVES)), dim3(LSE_WAVES * 64), 0, st,
-                           static_cast<const float*>(logits), ldv, labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok,
-                           w.lse, w.alpha, w.beta, w.ll, grad_out, grad_out_stride, scale, static_cast<float*>(grad), ldg, fastemit_lambda);
-    else
-        hipLaunchKernelGGL(rnnt_grad_kernel<bf16_t>, dim3(cdiv(rows, LSE_WAVES)), dim3(LSE_WAVES * 64), 0, st,
-                           static_cast<const bf16_t*>(logits), ldv, labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok,
-                           w.lse, w.alpha, w.beta, w.ll, grad_out, grad_out_stride, scale, static_cast<bf16_t*>(grad), ldg, fastemit_lambda);
+    by_dtype(dtype, [&](auto z) {
+        using TL = decltype(z);
+        hipLaunchKernelGGL(rnnt_grad_kernel<TL>, dim3(cdiv(rows, LSE_WAVES)), dim3(LSE_WAVES * 64), 0, st, static_cast<const TL*>(logits), ldv,
+                           labels, act_lens, label_lens, B, T, U1, V, blank, vec_ok, w.lse, w.alpha, w.beta, w.ll, grad_out, grad_out_stride,
+                           scale, static_cast<TL*>(grad), ldg, fastemit_lambda);
+    });
     ttmi_probe_end(2, st);
     TTMI_LAUNCH_CHECK("rnnt_grad_kernel");
     return TTMI_OK;
@@ -1175,12 +1081,11 @@ int ttmi_rnnt_align(const void* workspace, const int* act_lens, const int* label
     hipStream_t st = static_cast<hipStream_t>(stream);
     Ws w = carve(const_cast<void*>(workspace), B, T, U1);
     dec_t* dec = static_cast<dec_t*>(align_workspace);
-    int rc;
-    if (U1 <= 64) rc = launch_viterbi<1, 8>(st, B, w.lpb, w.lpl, act_lens, label_lens, T, U1, dec, frames, score);
-    else if (U1 <= 128) rc = launch_viterbi<2, 8>(st, B, w.lpb, w.lpl, act_lens, label_lens, T, U1, dec, frames, score);
-    else if (U1 <= 256) rc = launch_viterbi<4, 4>(st, B, w.lpb, w.lpl, act_lens, label_lens, T, U1, dec, frames, score);
-    else if (U1 <= 512) rc = launch_viterbi<8, 2>(st, B, w.lpb, w.lpl, act_lens, label_lens, T, U1, dec, frames, score);
-    else rc = launch_viterbi<16, 1>(st, B, w.lpb, w.lpl, act_lens, label_lens, T, U1, dec, frames, score);
+    const int rc = with_slots(U1, [&](auto R, auto PF) {
+        return launch_dec_lds("rnnt align", rnnt_viterbi_kernel<R, PF, true>, rnnt_viterbi_kernel<R, PF, false>, vit_dec_bytes(T, U1),
+                              g_align_debug, dim3(B), dim3(64), st, w.lpb, w.lpl, act_lens, label_lens, T, U1, (U1 + 63) / 64, dec, frames,
+                              score);
+    });
     if (rc) return rc;
     TTMI_LAUNCH_CHECK("rnnt_viterbi_kernel");
     return TTMI_OK;
