@@ -112,6 +112,22 @@ def _warn_no_exp(Bc, T, U1, J, V):
                   "joint + loss form runs instead" % (Bc, T, U1, J, V))
 
 
+def _scaled_param_grads(params, grads, gout):
+    """the parameter part of what backward() of the fused loss ops returns: per parameter grads[i] * gout, or None where the product was
+    added straight into the parameter's .grad (FlatModel's flat gradient buffer) and its gradient-ready callback run"""
+    rets = []
+    for prm, gp in zip(params, grads):
+        if getattr(prm, "_ttmi_direct", False) and prm.grad is not None:       # FlatModel: accumulate into the flat gradient buffer
+            prm.grad.addcmul_(gp, gout)
+            rets.append(None)
+            cb = getattr(prm, "_ttmi_on_grad", None)
+            if cb is not None:
+                cb()
+        else:
+            rets.append(gp * gout)
+    return rets
+
+
 class _JointLossFn(torch.autograd.Function):
     """joint network + RNN-T loss as ONE op that never holds the [B, T, U+1, V] logits: the batch is cut into chunks
     of utterances; per chunk the logits are produced (ttmi_joint_fwd), reduced to the lattice (ttmi_rnnt_loss_fwd), overwritten IN PLACE
@@ -138,9 +154,9 @@ class _JointLossFn(torch.autograd.Function):
         adding scale * distill_weight * d KD onto that gradient, joint_bwd.  A second chunk buffer is alive meanwhile; the 2 GB budget of
         default_loss_chunk leaves room for it, so the chunk size is the same.  No exp-domain form"""
         fe = ops.check_fastemit(fastemit_lambda)
-        mono = ops.check_topology(topology, fe) == "monotonic"
-        if mono and exp_state is not None:
-            raise ValueError("topology='monotonic' has no exp-domain form")
+        lat = ops.lattice(topology, fe)
+        if not lat.has_exp_forms and exp_state is not None:
+            raise ValueError("topology='%s' has no exp-domain form" % lat.name)
         kd = distill is not None and float(distill_weight) != 0.0
         if kd and exp_state is not None:
             raise ValueError("distill has no exp-domain form")
@@ -170,32 +186,8 @@ class _JointLossFn(torch.autograd.Function):
         for c0 in range(0, B, chunk):
             c1 = min(B, c0 + chunk)
             lab, al, ll = labels[c0:c1], act_lens[c0:c1], label_lens[c0:c1]
-            if kd:
-                ws = (ops.mono_workspace if mono else ops.rnnt_workspace)(c1 - c0, T, U1, enc.device)
-                kws = ops.kd_workspace(c1 - c0, T, U1, enc.device)
-                logits, saved = ops.joint_fwd(enc[c0:c1], dec[c0:c1], wf_, bf_, wp_, bp_, prec)
-                costs[c0:c1] = (ops.mono_loss_fwd if mono else ops.rnnt_loss_fwd)(logits, lab, al, ll, blank, ws)
-                kd_costs[c0:c1] = ops.kd_loss_fwd(logits, lab, al, ll, blank, distill[c0:c1], kws)
-                if need:
-                    if mono:
-                        grad = ops.mono_loss_bwd(logits, lab, al, ll, blank, ws, *upstream(c0, c1), scale, inplace=False)
-                    else:
-                        grad = ops.rnnt_loss_bwd(logits, lab, al, ll, blank, ws, *upstream(c0, c1), scale, inplace=False, fastemit_lambda=fe)
-                    grad = ops.kd_loss_bwd(logits, lab, al, ll, blank, kws, one, 0, scale * float(distill_weight), accumulate=grad)
-                    ops.joint_bwd(grad, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
-                    del grad
-                del logits, saved
-                continue
-            if mono:
-                ws = ops.mono_workspace(c1 - c0, T, U1, enc.device)
-                logits, saved = ops.joint_fwd(enc[c0:c1], dec[c0:c1], wf_, bf_, wp_, bp_, prec)
-                costs[c0:c1] = ops.mono_loss_fwd(logits, lab, al, ll, blank, ws)
-                if need:
-                    grad = ops.mono_loss_bwd(logits, lab, al, ll, blank, ws, *upstream(c0, c1), scale, inplace=True)
-                    ops.joint_bwd(grad, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
-                del logits, saved
-                continue
-            ws = ops.rnnt_workspace(c1 - c0, T, U1, enc.device)
+            ws = lat.workspace(c1 - c0, T, U1, enc.device)
+            kws = ops.kd_workspace(c1 - c0, T, U1, enc.device) if kd else None
             exp_ok = st is not None and ops.joint_exp_supported(c1 - c0, T, U1, J, V, prec, fwd_only=not need)
             if st is not None and not exp_ok:
                 _warn_no_exp(c1 - c0, T, U1, J, V)
@@ -211,17 +203,24 @@ class _JointLossFn(torch.autograd.Function):
                 exp_ran = True
                 continue
             logits, saved = ops.joint_fwd(enc[c0:c1], dec[c0:c1], wf_, bf_, wp_, bp_, prec)
-            costs[c0:c1] = ops.rnnt_loss_fwd(logits, lab, al, ll, blank, ws)
+            costs[c0:c1] = lat.loss_fwd(logits, lab, al, ll, blank, ws)
+            if kd:
+                kd_costs[c0:c1] = ops.kd_loss_fwd(logits, lab, al, ll, blank, distill[c0:c1], kws)
             if st is not None and not st.valid:                 # the plain form's log-sum-exp pass seeds the shift for the next step
                 ops.rnnt_shift_seed(ws, al, ll, c1 - c0, T, U1, st.nxt)
                 seeded = True
-            if need and ops.joint_loss_split_supported(logits, wf_.shape[0], prec):
+            if need and lat.has_exp_forms and not kd and ops.joint_loss_split_supported(logits, wf_.shape[0], prec):
                 # bf16x3: the gradient leaves the loss kernel as the two bf16 planes the joint's three-term backward multiplies (round 6: no split pass over d logits)
                 planes = ops.rnnt_loss_bwd_split(logits, lab, al, ll, blank, ws, *upstream(c0, c1), scale, fastemit_lambda=fe)
                 ops.joint_bwd_split(planes, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
             elif need:
-                grad = ops.rnnt_loss_bwd(logits, lab, al, ll, blank, ws, *upstream(c0, c1), scale, inplace=True, fastemit_lambda=fe)
+                # in place, unless the KD gradient is to be added: that one needs the logits once more
+                grad = lat.loss_bwd(logits, lab, al, ll, blank, ws, *upstream(c0, c1), scale, inplace=not kd, **lat.fastemit_kw(fe))
+                if kd:
+                    grad = ops.kd_loss_bwd(logits, lab, al, ll, blank, kws, one, 0, scale * float(distill_weight), accumulate=grad)
                 ops.joint_bwd(grad, enc[c0:c1], dec[c0:c1], wf_, wp_, saved, prec, g, out=(denc[c0:c1], ddec[c0:c1]))
+                if kd:
+                    del grad                # (the second chunk buffer)
             del logits, saved
         if st is not None and (exp_ran or seeded):
             st.cur.copy_(st.nxt)
@@ -250,16 +249,7 @@ class _JointLossFn(torch.autograd.Function):
         if gout.numel() != 1:
             raise NotImplementedError("fused joint + loss: per-utterance upstream gradients (reduction='none') are not supported; "
                                       "use model(inputs, targets) + RNNTLoss(reduction='none')")
-        rets = []
-        for prm, gp in zip(ctx.params, gs):
-            if getattr(prm, "_ttmi_direct", False) and prm.grad is not None:       # FlatModel: accumulate into the flat gradient buffer
-                prm.grad.addcmul_(gp, gout)
-                rets.append(None)
-                cb = getattr(prm, "_ttmi_on_grad", None)
-                if cb is not None:
-                    cb()
-            else:
-                rets.append(gp * gout)
+        rets = _scaled_param_grads(ctx.params, gs, gout)
         return (denc * gout, ddec * gout, *rets, None, None, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
@@ -303,16 +293,7 @@ class _CTCHeadLossFn(torch.autograd.Function):
         if gout.numel() != 1:
             raise NotImplementedError("fused CTC head + loss: per-utterance upstream gradients (reduction='none') are not supported; "
                                       "use model.ctc_head(enc_state) + ttmi.ctc.ctc_loss(reduction='none')")
-        rets = []
-        for prm, gp in zip(ctx.params, gs):
-            if getattr(prm, "_ttmi_direct", False) and prm.grad is not None:       # FlatModel: accumulate into the flat gradient buffer
-                prm.grad.addcmul_(gp, gout)
-                rets.append(None)
-                cb = getattr(prm, "_ttmi_on_grad", None)
-                if cb is not None:
-                    cb()
-            else:
-                rets.append(gp * gout)
+        rets = _scaled_param_grads(ctx.params, gs, gout)
         return (denc * gout, *rets, None, None, None, None, None, None, None)
 
 
@@ -325,9 +306,9 @@ def _joint_align(joint, enc, dec, labels, act_lens, label_lens, prec, chunk, bla
     read per call).  topology='monotonic': per chunk ttmi_joint_fwd + ttmi_mono_loss_fwd + ttmi_mono_align (+ ttmi_mono_emit_stats) on the
     one-decision-per-frame lattice; that lattice has no exp-domain branch.  -> warprnnt_pytorch.AlignResult"""
     from warprnnt_pytorch import AlignResult
-    mono = ops.check_topology(topology) == "monotonic"
-    if mono and exp_state is not None:
-        raise ValueError("topology='monotonic' has no exp-domain form")
+    lat = ops.lattice(topology)
+    if not lat.has_exp_forms and exp_state is not None:
+        raise ValueError("topology='%s' has no exp-domain form" % lat.name)
     with torch.no_grad():
         enc, dec = enc.detach().contiguous(), dec.detach().contiguous()
         wf, bf, wp, bp = (t.detach() for t in (joint.forward_layer.weight, joint.forward_layer.bias, joint.project_layer.weight,
@@ -349,27 +330,18 @@ def _joint_align(joint, enc, dec, labels, act_lens, label_lens, prec, chunk, bla
             c1 = min(B, c0 + chunk)
             n = c1 - c0
             lab, al, ll = labels[c0:c1], act_lens[c0:c1], label_lens[c0:c1]
-            if mono:
-                ws = ops.mono_workspace(n, T, U1, dev)
-                logits, saved = ops.joint_fwd(enc[c0:c1], dec[c0:c1], wf, bf, wp, bp, prec)
-                cost[c0:c1] = ops.mono_loss_fwd(logits, lab, al, ll, blank, ws)
-                del logits, saved
-                frames[c0:c1], score[c0:c1] = ops.mono_align(ws, al, ll, n, T, U1)
-                if stats:
-                    expected[c0:c1], mass[c0:c1] = ops.mono_emit_stats(ws, al, ll, n, T, U1)
-                return
-            ws = ops.rnnt_workspace(n, T, U1, dev)
+            ws = lat.workspace(n, T, U1, dev)
             if exp:
                 P, rowsum, saved, emis = ops.joint_fwd_exp(enc[c0:c1], dec[c0:c1], wf, bf, wp, bp, prec, exp_state.cur, lab.contiguous(), blank)
                 cost[c0:c1] = ops.rnnt_loss_fwd_exp(P, rowsum, lab, al, ll, blank, ws, exp_state.cur, None, emis, flags[i:i + 1])
                 del P, rowsum, saved, emis
             else:
                 logits, saved = ops.joint_fwd(enc[c0:c1], dec[c0:c1], wf, bf, wp, bp, prec)
-                cost[c0:c1] = ops.rnnt_loss_fwd(logits, lab, al, ll, blank, ws)
+                cost[c0:c1] = lat.loss_fwd(logits, lab, al, ll, blank, ws)
                 del logits, saved
-            frames[c0:c1], score[c0:c1] = ops.rnnt_align(ws, al, ll, n, T, U1)
+            frames[c0:c1], score[c0:c1] = lat.align(ws, al, ll, n, T, U1)
             if stats:
-                expected[c0:c1], mass[c0:c1] = ops.rnnt_emit_stats(ws, al, ll, n, T, U1)
+                expected[c0:c1], mass[c0:c1] = lat.emit_stats(ws, al, ll, n, T, U1)
 
         ran_exp = []
         for i, c0 in enumerate(starts):
@@ -488,12 +460,8 @@ class DeferredLogits(torch.Tensor):
         j = self._joint
         B, T, U1 = self.shape[0], self.shape[1], self.shape[2]
         ops.weights_fresh()
-        if topology == "monotonic":         # the plain (non-exp) chunk form, at the memory form's chunk size
-            chunk = j.default_loss_chunk(B, T, U1, False, self._prec)
-            return _JointLossFn.apply(self._enc, self._dec, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
-                                      j.project_layer.bias, labels, act_lens, label_lens, self._prec, int(chunk), reduction, None, grad,
-                                      int(blank), fastemit_lambda, None, topology)
-        exp = self._prec == 1 and os.environ.get("TTMI_DEFERRED_EXP", "1") != "0"
+        # (a lattice without the exp-domain form: the plain chunk form, at the memory form's chunk size)
+        exp = ops.lattice(topology).has_exp_forms and self._prec == 1 and os.environ.get("TTMI_DEFERRED_EXP", "1") != "0"
         chunk = j.default_loss_chunk(B, T, U1, exp, self._prec)
         if exp and not ops.joint_exp_supported(chunk, T, U1, j.forward_layer.out_features, j.project_layer.out_features, self._prec,
                                                fwd_only=not (grad and self.requires_grad)):
@@ -502,7 +470,7 @@ class DeferredLogits(torch.Tensor):
             chunk = j.default_loss_chunk(B, T, U1, False, self._prec)
         return _JointLossFn.apply(self._enc, self._dec, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
                                   j.project_layer.bias, labels, act_lens, label_lens, self._prec, int(chunk), reduction,
-                                  j.exp_shift_state(self._enc.device) if exp else None, grad, int(blank), fastemit_lambda)
+                                  j.exp_shift_state(self._enc.device) if exp else None, grad, int(blank), fastemit_lambda, None, topology)
 
     def rnnt_align(self, labels, act_lens, label_lens, blank=0, *, stats=False, topology="rnnt"):
         """forced alignment on this handle's logits without forming them (called by warprnnt_pytorch.rnnt_align; arguments already
@@ -514,18 +482,14 @@ class DeferredLogits(torch.Tensor):
         j = self._joint
         B, T, U1 = self.shape[0], self.shape[1], self.shape[2]
         ops.weights_fresh()
-        if ops.check_topology(topology) == "monotonic":
-            chunk = j.default_loss_chunk(B, T, U1, False, self._prec)
-            return _joint_align(j, self._enc, self._dec, labels, act_lens, label_lens, self._prec, int(chunk), int(blank), None, stats,
-                                "monotonic")
-        exp = self._prec == 1 and os.environ.get("TTMI_DEFERRED_EXP", "1") != "0"
+        exp = ops.lattice(topology).has_exp_forms and self._prec == 1 and os.environ.get("TTMI_DEFERRED_EXP", "1") != "0"
         st = j.exp_shift_state(self._enc.device) if exp else None
         exp = exp and st.valid
         chunk = j.default_loss_chunk(B, T, U1, exp, self._prec)
         if exp and not ops.joint_exp_supported(chunk, T, U1, j.forward_layer.out_features, j.project_layer.out_features, self._prec, fwd_only=True):
             exp, chunk = False, j.default_loss_chunk(B, T, U1, False, self._prec)
         return _joint_align(j, self._enc, self._dec, labels, act_lens, label_lens, self._prec, int(chunk), int(blank), st if exp else None,
-                            stats)
+                            stats, topology)
 
     @classmethod
     def __torch_function__(cls, func, types, args=(), kwargs=None):
@@ -767,9 +731,9 @@ class Transducer(nn.Module):
         shape, dtype or device."""
         from warprnnt_pytorch import check_lengths as certify, check_monotonic_lengths as monotonic_lengths
         fastemit_lambda = ops.check_fastemit(fastemit_lambda)
-        mono = ops.check_topology(topology, fastemit_lambda) == "monotonic"
-        if mono and exp_domain:
-            raise ValueError("topology='monotonic' has no exp-domain form: leave exp_domain off")
+        lat = ops.lattice(topology, fastemit_lambda)
+        if exp_domain and not lat.has_exp_forms:
+            raise ValueError("topology='%s' has no exp-domain form: leave exp_domain off" % lat.name)
         distill_weight = self._distill_weight(distill_weight)
         if distill is None or distill_weight == 0.0:
             distill, distill_weight = None, 0.0
@@ -782,7 +746,7 @@ class Transducer(nn.Module):
         B, T, U1 = enc_state.shape[0], enc_state.shape[1], dec_state.shape[1]
         labels, al, ll = (t.to(device=enc_state.device, dtype=torch.int32).contiguous() for t in (targets, inputs_length, targets_length))
         certify(labels, al, ll, B, T, U1, check_lengths)
-        if mono and check_lengths:
+        if lat.label_takes_frame and check_lengths:
             monotonic_lengths(al, ll)                # ValueError for an utterance with more labels than frames
         ops.weights_fresh()
         prec = default_precision()
@@ -792,16 +756,10 @@ class Transducer(nn.Module):
         if distill is not None:
             from ttmi.distill import check_teacher
             distill = check_teacher(distill, B, T, U1)
-            rnnt = _JointLossFn.apply(enc_state, dec_state, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
-                                      j.project_layer.bias, labels, al, ll, prec, int(chunk), reduction, None, torch.is_grad_enabled(), 0,
-                                      fastemit_lambda, utterance_weights, topology, distill, distill_weight)
-            if ctc_weight > 0.0:
-                return rnnt + ctc_weight * self._ctc_from_states(enc_state, labels, al, ll, reduction)
-            return rnnt
         rnnt = _JointLossFn.apply(enc_state, dec_state, j.forward_layer.weight, j.forward_layer.bias, j.project_layer.weight,
                                   j.project_layer.bias, labels, al, ll, prec, int(chunk), reduction,
                                   j.exp_shift_state(enc_state.device) if exp_domain and prec == 1 else None, torch.is_grad_enabled(), 0,
-                                  fastemit_lambda, utterance_weights, topology)
+                                  fastemit_lambda, utterance_weights, topology, distill, distill_weight)
         if ctc_weight > 0.0:
             return rnnt + ctc_weight * self._ctc_from_states(enc_state, labels, al, ll, reduction)
         return rnnt
@@ -1068,24 +1026,7 @@ class Transducer(nn.Module):
         forward, so "does not disturb training" is a statement about the shift state only.
 
         This is the standard lattice; `align_monotonic` is the same call on the one-decision-per-frame lattice of the decoders."""
-        from warprnnt_pytorch import check_lengths as certify
-        labels, al, ll = (t.to(dtype=torch.int32) for t in (targets, inputs_length, targets_length))
-        certify(labels.contiguous(), al.contiguous(), ll.contiguous(), inputs.shape[0], 0, targets.shape[1] + 1, False)
-        if not inputs.is_cuda:
-            raise ValueError("Transducer.align: inputs must live on the GPU (the MI355X build has no CPU path)")
-        with torch.no_grad():
-            enc_state, dec_state = self._encode(inputs, targets)
-        B, T, U1 = enc_state.shape[0], enc_state.shape[1], dec_state.shape[1]
-        labels, al, ll = (t.to(device=enc_state.device).contiguous() for t in (labels, al, ll))
-        certify(labels, al, ll, B, T, U1, check_lengths)
-        ops.weights_fresh()
-        prec = default_precision()
-        st = self.joint.exp_shift_state(enc_state.device) if exp_domain and prec == 1 else None
-        if st is not None and not st.valid:
-            st = None
-        if chunk is None:
-            chunk = self.default_loss_chunk(B, T, U1, st is not None)
-        return _joint_align(self.joint, enc_state, dec_state, labels, al, ll, prec, int(chunk), 0, st, stats)
+        return self._align("align", "rnnt", inputs, inputs_length, targets, targets_length, chunk, check_lengths, exp_domain, stats)
 
     def align_monotonic(self, inputs, inputs_length, targets, targets_length, chunk=None, check_lengths=True, *, stats=False):
         """`align` on the one-decision-per-frame lattice that loss(topology='monotonic') trains and that recognize / decode_batch / the beam
@@ -1097,22 +1038,31 @@ class Transducer(nn.Module):
         exp-domain form.  Under check_lengths an utterance with more labels than frames is a ValueError; with the check off it has score
         -inf, cost +inf, every frames / expected_frames entry -1 and mass 0.  (A method of its own and not a keyword of `align`, whose
         parameter list is pinned; warprnnt_pytorch.rnnt_align takes topology='monotonic' for the same alignment on logits or a handle.)"""
+        return self._align("align_monotonic", "monotonic", inputs, inputs_length, targets, targets_length, chunk, check_lengths, False, stats)
+
+    def _align(self, method, topology, inputs, inputs_length, targets, targets_length, chunk, check_lengths, exp_domain, stats):
+        """the body of align / align_monotonic (`method`: the caller's name, for its error message)"""
         from warprnnt_pytorch import check_lengths as certify, check_monotonic_lengths as monotonic_lengths
+        lat = ops.lattice(topology)
         labels, al, ll = (t.to(dtype=torch.int32) for t in (targets, inputs_length, targets_length))
         certify(labels.contiguous(), al.contiguous(), ll.contiguous(), inputs.shape[0], 0, targets.shape[1] + 1, False)
         if not inputs.is_cuda:
-            raise ValueError("Transducer.align_monotonic: inputs must live on the GPU (the MI355X build has no CPU path)")
+            raise ValueError("Transducer.%s: inputs must live on the GPU (the MI355X build has no CPU path)" % method)
         with torch.no_grad():
             enc_state, dec_state = self._encode(inputs, targets)
         B, T, U1 = enc_state.shape[0], enc_state.shape[1], dec_state.shape[1]
         labels, al, ll = (t.to(device=enc_state.device).contiguous() for t in (labels, al, ll))
         certify(labels, al, ll, B, T, U1, check_lengths)
-        if check_lengths:
+        if lat.label_takes_frame and check_lengths:
             monotonic_lengths(al, ll)                # ValueError for an utterance with more labels than frames
         ops.weights_fresh()
+        prec = default_precision()
+        st = self.joint.exp_shift_state(enc_state.device) if exp_domain and lat.has_exp_forms and prec == 1 else None
+        if st is not None and not st.valid:
+            st = None
         if chunk is None:
-            chunk = self.default_loss_chunk(B, T, U1, False)
-        return _joint_align(self.joint, enc_state, dec_state, labels, al, ll, default_precision(), int(chunk), 0, None, stats, "monotonic")
+            chunk = self.default_loss_chunk(B, T, U1, st is not None)
+        return _joint_align(self.joint, enc_state, dec_state, labels, al, ll, prec, int(chunk), 0, st, stats, topology)
 
     def default_loss_chunk(self, B, T, U1, exp_domain=False):
         """utterances per chunk of `loss()` (JointNet.default_loss_chunk)"""

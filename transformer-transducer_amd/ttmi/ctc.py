@@ -50,19 +50,12 @@ class _CTCLossFn(torch.autograd.Function):
         ctx.blank, ctx.reduction, ctx.in_dtype = blank, reduction, logits.dtype
         if zero_infinity:       # (the kernels give an infeasible utterance an all-zero gradient either way)
             costs = torch.where(torch.isinf(costs), torch.zeros_like(costs), costs)
-        if reduction == "none":
-            return costs
-        out = costs.sum().reshape(1)
-        return out / B if reduction == "mean" else out
+        return ops.reduce_costs(costs, reduction)
 
     @staticmethod
     def backward(ctx, grad_out):
         x, labels, act_lens, label_lens, ws = ctx.saved_tensors
-        B = x.shape[0]
-        go = grad_out.contiguous().float()
-        per_utt = ctx.reduction == "none"
-        scale = 1.0 / B if ctx.reduction == "mean" else 1.0
-        grad = ops.ctc_loss_bwd(x, labels, act_lens, label_lens, ctx.blank, ws, go, 1 if per_utt else 0, scale)
+        grad = ops.ctc_loss_bwd(x, labels, act_lens, label_lens, ctx.blank, ws, *ops.grad_out_args(grad_out, ctx.reduction, x.shape[0]))
         return grad.to(ctx.in_dtype), None, None, None, None, None, None
 
 

@@ -55,19 +55,12 @@ class _LatticeKDFn(torch.autograd.Function):
         costs = ops.kd_loss_fwd(acts_c, labels, act_lens, label_lens, blank, teacher, ws)
         ctx.save_for_backward(acts_c, labels, act_lens, label_lens, ws)
         ctx.blank, ctx.reduction = blank, reduction
-        if reduction == "none":
-            return costs
-        out = costs.sum().reshape(1)
-        return out / B if reduction == "mean" else out
+        return ops.reduce_costs(costs, reduction)
 
     @staticmethod
     def backward(ctx, grad_out):
         acts, labels, act_lens, label_lens, ws = ctx.saved_tensors
-        B = acts.shape[0]
-        go = grad_out.contiguous().float()
-        per_utt = ctx.reduction == "none"
-        scale = 1.0 / B if ctx.reduction == "mean" else 1.0
-        grad = ops.kd_loss_bwd(acts, labels, act_lens, label_lens, ctx.blank, ws, go, 1 if per_utt else 0, scale)
+        grad = ops.kd_loss_bwd(acts, labels, act_lens, label_lens, ctx.blank, ws, *ops.grad_out_args(grad_out, ctx.reduction, acts.shape[0]))
         return grad, None, None, None, None, None, None
 
 

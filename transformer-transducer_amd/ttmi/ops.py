@@ -75,25 +75,47 @@ def padded_empty(shape, dtype, device, multiple=64):
 # caching allocator happens to place where an earlier one lived must not inherit it.
 
 
-# ----------------------------------------------------------------------------- RNN-T loss
-def rnnt_workspace(B, T, U1, device):
-    n = lib().ttmi_rnnt_workspace_bytes(c_int(B), c_int(T), c_int(U1))
-    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+def _sized(name, *args, restype=ctypes.c_size_t):
+    """call a library entry that does not return an int status: a byte / float / row count (size_t unless `restype` says otherwise).  The
+    restype is set the first time the symbol is used and found in place afterwards"""
+    f = getattr(lib(), name)
+    if f.restype is not restype:
+        f.restype = restype
+    return f(*args)
 
 
-def rnnt_loss_fwd(logits, labels, act_lens, label_lens, blank, workspace):
-    """logits: f32/bf16 [B,T,U1,V], dense or row-padded view"""
-    _need_cuda(logits, labels, act_lens, label_lens, workspace)
-    B, T, U1, V = logits.shape
-    ld = row_pitch(logits)
+def grad_buffer(logits, inplace=False, zero_pad=True):
+    """where a loss gradient of `logits` ([..., V], dense or row-padded view) goes -> (grad, pitch): the logits themselves (inplace), a dense
+    tensor when the logits are dense, else the [..., :V] view of a new buffer of the logits' pitch.  zero_pad: the kernel that fills it
+    writes exact zeros into the pad columns, so a padded `grad` carries the `_ttmi_zero_pad` mark (above)"""
+    V, ld = logits.shape[-1], row_pitch(logits)
     assert ld is not None
-    costs = torch.empty(B, dtype=torch.float32, device=logits.device)
-    check(lib().ttmi_rnnt_loss_fwd(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
-                                   c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(costs), _stream()),
-          "ttmi_rnnt_loss_fwd")
-    return costs
+    if inplace:
+        grad = logits
+    elif ld == V:
+        grad = torch.empty_like(logits)
+    else:
+        grad = torch.empty(*logits.shape[:-1], ld, dtype=logits.dtype, device=logits.device)[..., :V]
+    if zero_pad and ld != V:
+        grad._ttmi_zero_pad = ld
+    return grad, ld
 
 
+def reduce_costs(costs, reduction):
+    """the two-call losses' reduction of per-utterance costs [B]: 'none' -> costs, 'sum' -> [1], 'mean' -> [1], the sum DIVIDED by B (the
+    fused ops of tt.model multiply by 1 / B instead: the last bit differs, and each keeps its own)"""
+    if reduction == "none":
+        return costs
+    out = costs.sum().reshape(1)
+    return out / costs.shape[0] if reduction == "mean" else out
+
+
+def grad_out_args(grad_out, reduction, B):
+    """the upstream gradient of reduce_costs' result -> the (grad_out, grad_out_stride, scale) arguments of a *_loss_bwd call"""
+    return grad_out.contiguous().float(), 1 if reduction == "none" else 0, 1.0 / B if reduction == "mean" else 1.0
+
+
+# ----------------------------------------------------------------------------- the transducer lattices (RNN-T loss, alignment, statistics)
 def check_fastemit(fastemit_lambda):
     """-> fastemit_lambda as a float; ValueError unless it is a finite number >= 0 (the library checks again)"""
     try:
@@ -105,111 +127,161 @@ def check_fastemit(fastemit_lambda):
     return v
 
 
+class Lattice:
+    """One transducer lattice the loss kernels walk: the library symbols of its six entries and the facts callers branch on.  The
+    underscored methods are the wrappers of both lattices, one body each; what differs between the lattices is said in each docstring.
+    lat.workspace / .loss_fwd / .loss_bwd / .align / .emit_stats are this module's rnnt_* / mono_* functions below."""
+    __slots__ = ("name", "prefix", "takes_fastemit", "has_exp_forms", "label_takes_frame", "symbols")
+    ENTRIES = ("workspace", "loss_fwd", "loss_bwd", "align", "emit_stats")
+
+    def __init__(self, name, prefix, takes_fastemit, has_exp_forms, label_takes_frame, **symbols):
+        # takes_fastemit: the gradient entry ends in a FastEmit weight; has_exp_forms: the exp-domain and bf16x3 split-plane chunk forms
+        # (rnnt_loss_fwd_exp / _bwd_exp / _bwd_split, rnnt_shift_seed below) exist for it; label_takes_frame: an utterance with more labels
+        # than frames has no path (the callers' length checks refuse it)
+        self.name, self.prefix, self.symbols = name, prefix, symbols
+        self.takes_fastemit, self.has_exp_forms, self.label_takes_frame = takes_fastemit, has_exp_forms, label_takes_frame
+
+    def __getattr__(self, entry):
+        # looked up by name at call time: whoever wraps ops.rnnt_loss_bwd (tests count calls that way) sees the calls made through a record too
+        if entry in Lattice.ENTRIES:
+            return globals()["%s_%s" % (self.prefix, entry)]
+        raise AttributeError(entry)
+
+    def fastemit_kw(self, fastemit_lambda):
+        """the keyword of lat.loss_bwd that only a lattice with a FastEmit gradient takes"""
+        return {"fastemit_lambda": fastemit_lambda} if self.takes_fastemit else {}
+
+    def _call(self, entry, *args):
+        sym = self.symbols[entry]
+        check(getattr(lib(), sym)(*args, _stream()), sym)
+
+    def _workspace(self, B, T, U1, device):
+        n = _sized(self.symbols["workspace"], c_int(B), c_int(T), c_int(U1))
+        return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+
+    def _loss_fwd(self, logits, labels, act_lens, label_lens, blank, workspace):
+        """logits: f32/bf16 [B,T,U1,V], dense or row-padded view -> costs f32 [B]; 'monotonic': on the decoders' one-symbol-per-frame lattice
+        (include/ttmi.h)"""
+        _need_cuda(logits, labels, act_lens, label_lens, workspace)
+        B, T, U1, V = logits.shape
+        ld = row_pitch(logits)
+        assert ld is not None
+        costs = torch.empty(B, dtype=torch.float32, device=logits.device)
+        self._call("loss_fwd", _p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T),
+                   c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(costs))
+        return costs
+
+    def _loss_bwd(self, logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, inplace=False, fastemit_lambda=0.0):
+        """inplace: the gradient overwrites the logits (same dtype and pitch; the fused joint + loss path needs them only once).
+        fastemit_lambda > 0: the FastEmit gradient (include/ttmi.h, ttmi_rnnt_loss_bwd_fe); 'monotonic' has none: neither ttmi_mono_loss_bwd
+        nor mono_loss_bwd takes such an argument"""
+        fe = check_fastemit(fastemit_lambda)
+        _need_cuda(logits, labels, act_lens, label_lens, workspace, grad_out)
+        B, T, U1, V = logits.shape
+        grad, ld = grad_buffer(logits, inplace)
+        self._call("loss_bwd", _p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T),
+                   c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(grad_out), c_int(grad_out_stride), c_float(scale), _p(grad), c_long(ld),
+                   *((c_float(fe),) if self.takes_fastemit else ()))
+        return grad
+
+    def _align(self, workspace, act_lens, label_lens, B, T, U1):
+        """best path through the lattice a finished loss_fwd (or rnnt_loss_fwd_exp) left in `workspace` (read only) -> (frames int32
+        [B, U1-1], -1 for u >= U_b; score f32 [B]: the path's log-probability).  'rnnt': frames[u] = the frame at which label u+1 is emitted,
+        non-decreasing.  'monotonic': the frame whose one decision is label u+1, STRICTLY increasing; score -inf with all frames -1 for an
+        utterance with more labels than frames.  The label move is taken only when strictly greater (a tie goes to blank); include/ttmi.h,
+        ttmi_rnnt_align / ttmi_mono_align"""
+        _need_cuda(workspace, act_lens, label_lens)
+        _trace(self.symbols["align"][5:], B, T, U1)
+        n = _sized(self.symbols["align_workspace"], c_int(B), c_int(T), c_int(U1))
+        aws = torch.empty((n + 7) // 8, dtype=torch.int64, device=workspace.device)
+        frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=workspace.device)
+        score = torch.empty(B, dtype=torch.float32, device=workspace.device)
+        self._call("align", _p(workspace), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U1), _p(aws), _p(frames), _p(score))
+        return frames, score
+
+    def _emit_stats(self, workspace, act_lens, label_lens, B, T, U1):
+        """per label, from the alpha / beta of a finished forward in `workspace` (read only) -> (expected f32 [B, U1-1]: expected emission frame,
+        -1 for u >= U_b; mass f32 [B, U1-1]: total emission posterior, 1 for a healthy lattice, 0 for u >= U_b); 'monotonic': an utterance
+        without a path has 0 / -1 in every entry"""
+        _need_cuda(workspace, act_lens, label_lens)
+        _trace(self.symbols["emit_stats"][5:], B, T, U1)
+        expected = torch.empty(B, U1 - 1, dtype=torch.float32, device=workspace.device)
+        mass = torch.empty(B, U1 - 1, dtype=torch.float32, device=workspace.device)
+        self._call("emit_stats", _p(workspace), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U1), _p(expected), _p(mass))
+        return expected, mass
+
+
+LATTICES = {
+    "rnnt": Lattice("rnnt", "rnnt", True, True, False, workspace="ttmi_rnnt_workspace_bytes", loss_fwd="ttmi_rnnt_loss_fwd", loss_bwd="ttmi_rnnt_loss_bwd_fe",
+                    align_workspace="ttmi_rnnt_align_workspace_bytes", align="ttmi_rnnt_align", emit_stats="ttmi_rnnt_emit_stats"),
+    "monotonic": Lattice("monotonic", "mono", False, False, True, workspace="ttmi_mono_workspace_bytes", loss_fwd="ttmi_mono_loss_fwd",
+                         loss_bwd="ttmi_mono_loss_bwd", align_workspace="ttmi_mono_align_workspace_bytes", align="ttmi_mono_align",
+                         emit_stats="ttmi_mono_emit_stats"),
+}
+TOPOLOGIES = tuple(LATTICES)
+
+
+def check_topology(topology, fastemit_lambda=0.0):
+    """-> topology; ValueError unless it names a lattice the loss kernels walk, or for FastEmit on the monotonic one (not built)"""
+    if topology not in TOPOLOGIES:
+        raise ValueError("topology must be 'rnnt' or 'monotonic', got %r" % (topology,))
+    if topology == "monotonic" and fastemit_lambda > 0.0:
+        raise ValueError("topology='monotonic' does not take fastemit_lambda > 0 (FastEmit is defined on the standard lattice here)")
+    return topology
+
+
+def lattice(topology, fastemit_lambda=0.0):
+    """-> the Lattice record of `topology`, after check_topology's checks"""
+    return LATTICES[check_topology(topology, fastemit_lambda)]
+
+
+# the per-lattice names of the wrappers above: what a record's entries resolve to, and what tests and tools call
+_RNNT, _MONO = LATTICES["rnnt"], LATTICES["monotonic"]
+
+
+def rnnt_workspace(B, T, U1, device):
+    return _RNNT._workspace(B, T, U1, device)
+
+
+def rnnt_loss_fwd(logits, labels, act_lens, label_lens, blank, workspace):
+    return _RNNT._loss_fwd(logits, labels, act_lens, label_lens, blank, workspace)
+
+
 def rnnt_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, inplace=False, fastemit_lambda=0.0):
-    """inplace: the gradient overwrites the logits (same dtype and pitch; the fused joint + loss path needs them only once).
-    fastemit_lambda > 0: the FastEmit gradient (include/ttmi.h, ttmi_rnnt_loss_bwd_fe)"""
-    fe = check_fastemit(fastemit_lambda)
-    _need_cuda(logits, labels, act_lens, label_lens, workspace, grad_out)
-    B, T, U1, V = logits.shape
-    ld = row_pitch(logits)
-    if inplace:
-        buf = grad = logits
-        ldg = ld
-    elif ld == V:
-        buf = grad = torch.empty_like(logits)
-        ldg = V
-    else:
-        buf = torch.empty(B, T, U1, ld, dtype=logits.dtype, device=logits.device)
-        grad, ldg = buf[..., :V], ld
-    check(lib().ttmi_rnnt_loss_bwd_fe(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
-                                      c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(grad_out),
-                                      c_int(grad_out_stride), c_float(scale), _p(grad), c_long(ldg), c_float(fe), _stream()),
-          "ttmi_rnnt_loss_bwd_fe")
-    if ldg != V:
-        grad._ttmi_zero_pad = ldg
-    return grad
+    return _RNNT._loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, inplace, fastemit_lambda)
 
 
-# ----------------------------------------------------------------------------- monotonic RNN-T loss (the decoders' one-symbol-per-frame lattice)
+def rnnt_align(workspace, act_lens, label_lens, B, T, U1):
+    return _RNNT._align(workspace, act_lens, label_lens, B, T, U1)
+
+
+def rnnt_emit_stats(workspace, act_lens, label_lens, B, T, U1):
+    return _RNNT._emit_stats(workspace, act_lens, label_lens, B, T, U1)
+
+
 def mono_workspace(B, T, U1, device):
-    f = lib().ttmi_mono_workspace_bytes
-    f.restype = ctypes.c_size_t
-    n = f(c_int(B), c_int(T), c_int(U1))
-    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+    return _MONO._workspace(B, T, U1, device)
 
 
 def mono_loss_fwd(logits, labels, act_lens, label_lens, blank, workspace):
-    """logits: f32/bf16 [B,T,U1,V], dense or row-padded view -> costs f32 [B] on the monotonic lattice (include/ttmi.h)"""
-    _need_cuda(logits, labels, act_lens, label_lens, workspace)
-    B, T, U1, V = logits.shape
-    ld = row_pitch(logits)
-    assert ld is not None
-    costs = torch.empty(B, dtype=torch.float32, device=logits.device)
-    check(lib().ttmi_mono_loss_fwd(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
-                                   c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(costs), _stream()),
-          "ttmi_mono_loss_fwd")
-    return costs
+    return _MONO._loss_fwd(logits, labels, act_lens, label_lens, blank, workspace)
 
 
 def mono_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, inplace=False):
-    """inplace: the gradient overwrites the logits (same dtype and pitch), as in rnnt_loss_bwd"""
-    _need_cuda(logits, labels, act_lens, label_lens, workspace, grad_out)
-    B, T, U1, V = logits.shape
-    ld = row_pitch(logits)
-    assert ld is not None
-    if inplace:
-        buf = grad = logits
-        ldg = ld
-    elif ld == V:
-        buf = grad = torch.empty_like(logits)
-        ldg = V
-    else:
-        buf = torch.empty(B, T, U1, ld, dtype=logits.dtype, device=logits.device)
-        grad, ldg = buf[..., :V], ld
-    check(lib().ttmi_mono_loss_bwd(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
-                                   c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(grad_out),
-                                   c_int(grad_out_stride), c_float(scale), _p(grad), c_long(ldg), _stream()),
-          "ttmi_mono_loss_bwd")
-    if ldg != V:
-        grad._ttmi_zero_pad = ldg
-    return grad
+    return _MONO._loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, inplace)
 
 
 def mono_align(workspace, act_lens, label_lens, B, T, U1):
-    """rnnt_align on the monotonic lattice: the best path through the lattice a finished mono_loss_fwd left in `workspace` (read only) ->
-    (frames int32 [B, U1-1]: the frame whose one decision is label u+1, STRICTLY increasing, -1 for u >= U_b; score f32 [B]: the path's
-    log-probability, -inf with all frames -1 for an utterance with more labels than frames).  The label move is taken only when strictly
-    greater (a tie goes to blank); include/ttmi.h, ttmi_mono_align"""
-    _need_cuda(workspace, act_lens, label_lens)
-    _trace("mono_align", B, T, U1)
-    f = lib().ttmi_mono_align_workspace_bytes
-    f.restype = ctypes.c_size_t
-    aws = torch.empty((f(c_int(B), c_int(T), c_int(U1)) + 7) // 8, dtype=torch.int64, device=workspace.device)
-    frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=workspace.device)
-    score = torch.empty(B, dtype=torch.float32, device=workspace.device)
-    check(lib().ttmi_mono_align(_p(workspace), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U1), _p(aws), _p(frames), _p(score),
-                                _stream()), "ttmi_mono_align")
-    return frames, score
+    return _MONO._align(workspace, act_lens, label_lens, B, T, U1)
 
 
 def mono_emit_stats(workspace, act_lens, label_lens, B, T, U1):
-    """rnnt_emit_stats on the monotonic lattice, from the alpha / beta of a finished mono_loss_fwd in `workspace` (read only) -> (expected
-    f32 [B, U1-1]: expected emission frame, -1 for u >= U_b; mass f32 [B, U1-1]: total emission posterior, 1 for a healthy lattice, 0 for
-    u >= U_b); an utterance without a path has 0 / -1 in every entry"""
-    _need_cuda(workspace, act_lens, label_lens)
-    _trace("mono_emit_stats", B, T, U1)
-    expected = torch.empty(B, U1 - 1, dtype=torch.float32, device=workspace.device)
-    mass = torch.empty(B, U1 - 1, dtype=torch.float32, device=workspace.device)
-    check(lib().ttmi_mono_emit_stats(_p(workspace), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U1), _p(expected), _p(mass),
-                                     _stream()), "ttmi_mono_emit_stats")
-    return expected, mass
+    return _MONO._emit_stats(workspace, act_lens, label_lens, B, T, U1)
 
 
 # ----------------------------------------------------------------------------- distillation on collapsed lattice posteriors (csrc/distill.hip)
 def kd_workspace(B, T, U1, device):
-    f = lib().ttmi_kd_workspace_bytes
-    f.restype = ctypes.c_size_t
-    n = f(c_int(B), c_int(T), c_int(U1))
+    n = _sized("ttmi_kd_workspace_bytes", c_int(B), c_int(T), c_int(U1))
     return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
 
 
@@ -276,41 +348,26 @@ def kd_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_out
         if accumulate.shape != logits.shape or accumulate.dtype != logits.dtype or row_pitch(accumulate) is None:
             raise ValueError("kd_loss_bwd: accumulate must have the logits' shape and dtype (dense or row-padded)")
         grad, ldg = accumulate, row_pitch(accumulate)
-    elif inplace:
-        grad, ldg = logits, ld
-    elif ld == V:
-        grad, ldg = torch.empty_like(logits), V
     else:
-        buf = torch.empty(B, T, U1, ld, dtype=logits.dtype, device=logits.device)
-        grad, ldg = buf[..., :V], ld
+        grad, ldg = grad_buffer(logits, inplace)
     _trace("kd_loss_bwd", B, T, U1, V)
     check(lib().ttmi_kd_loss_bwd(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens),
                                  c_int(B), c_int(T), c_int(U1), c_int(V), c_int(blank), _p(workspace), _p(grad_out),
                                  c_int(grad_out_stride), c_float(scale), _p(grad), c_long(ldg), c_int(0 if accumulate is None else 1),
                                  _stream()), "ttmi_kd_loss_bwd")
-    if accumulate is None and ldg != V:
-        grad._ttmi_zero_pad = ldg
     return grad
-
-
-TOPOLOGIES = ("rnnt", "monotonic")
-
-
-def check_topology(topology, fastemit_lambda=0.0):
-    """-> topology; ValueError unless it names a lattice the loss kernels walk, or for FastEmit on the monotonic one (not built)"""
-    if topology not in TOPOLOGIES:
-        raise ValueError("topology must be 'rnnt' or 'monotonic', got %r" % (topology,))
-    if topology == "monotonic" and fastemit_lambda > 0.0:
-        raise ValueError("topology='monotonic' does not take fastemit_lambda > 0 (FastEmit is defined on the standard lattice here)")
-    return topology
 
 
 # ----------------------------------------------------------------------------- CTC loss / greedy decode (auxiliary head on the audio encoder)
 def ctc_workspace(B, T, U, device):
-    f = lib().ttmi_ctc_workspace_bytes
-    f.restype = ctypes.c_size_t
-    n = f(c_int(B), c_int(T), c_int(U))
+    n = _sized("ttmi_ctc_workspace_bytes", c_int(B), c_int(T), c_int(U))
     return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+
+
+def _ctc_labels(labels, B):
+    if labels.dim() != 2 or labels.shape[0] != B or labels.dtype is not torch.int32 or (labels.numel() and not labels.is_contiguous()):
+        raise ValueError("ctc: labels must be contiguous int32 [B, U]")
+    return labels.shape[1]
 
 
 def _ctc_args(logits, labels):
@@ -319,8 +376,7 @@ def _ctc_args(logits, labels):
     ld = row_pitch(logits)
     if ld is None:
         raise ValueError("ctc: logits must be dense or a [..., :V] view of a row-padded buffer")
-    if labels.dim() != 2 or labels.shape[0] != logits.shape[0] or labels.dtype is not torch.int32 or (labels.numel() and not labels.is_contiguous()):
-        raise ValueError("ctc: labels must be contiguous int32 [B, U]")
+    _ctc_labels(labels, logits.shape[0])
     return ld
 
 
@@ -341,12 +397,7 @@ def ctc_loss_bwd(logits, labels, act_lens, label_lens, blank, workspace, grad_ou
     _need_cuda(logits, labels, act_lens, label_lens, workspace, grad_out)
     ld = _ctc_args(logits, labels)
     B, T, V = logits.shape
-    if inplace:
-        grad = logits
-    elif ld == V:
-        grad = torch.empty_like(logits)
-    else:
-        grad = torch.empty(B, T, ld, dtype=logits.dtype, device=logits.device)[..., :V]
+    grad, _ = grad_buffer(logits, inplace, zero_pad=False)
     check(lib().ttmi_ctc_loss_bwd(_p(logits), c_long(ld), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(labels.shape[1]),
                                   c_int(V), c_int(blank), _p(workspace), _p(grad_out), c_int(grad_out_stride), c_float(scale), _p(grad),
                                   c_long(ld), _stream()), "ttmi_ctc_loss_bwd")
@@ -370,9 +421,7 @@ def ctc_greedy(logits, act_lens, blank=0):
 
 def ctc_align_workspace(B, T, U, device):
     """scratch of ctc_align (decision words when they do not fit LDS): int64 words, never empty (the entry wants a pointer whatever the shape)"""
-    f = lib().ttmi_ctc_align_workspace_bytes
-    f.restype = ctypes.c_size_t
-    n = f(c_int(B), c_int(T), c_int(U))
+    n = _sized("ttmi_ctc_align_workspace_bytes", c_int(B), c_int(T), c_int(U))
     return torch.empty(max((n + 7) // 8, 1), dtype=torch.int64, device=device)
 
 
@@ -382,9 +431,7 @@ def ctc_align(workspace, labels, act_lens, label_lens, B, T, V, blank=0, align_w
     f32 [B]: the path's log-probability).  An utterance with no feasible alignment: score -inf, every path / spans entry -1.  Predecessors
     are tried in the order s, s-1, s-2 and replaced only when strictly greater (include/ttmi.h, ttmi_ctc_align)"""
     _need_cuda(workspace, labels, act_lens, label_lens)
-    if labels.dim() != 2 or labels.shape[0] != B or labels.dtype is not torch.int32 or (labels.numel() and not labels.is_contiguous()):
-        raise ValueError("ctc: labels must be contiguous int32 [B, U]")
-    U = labels.shape[1]
+    U = _ctc_labels(labels, B)
     _trace("ctc_align", B, T, U)
     aws = ctc_align_workspace(B, T, U, workspace.device) if align_workspace is None else align_workspace
     path = torch.empty(B, T, dtype=torch.int32, device=workspace.device)
@@ -400,9 +447,7 @@ def ctc_emit_stats(workspace, labels, act_lens, label_lens, B, T, V, blank=0):
     -1 for u >= U_b; mass f32 [B, U]: total onset posterior, 1 for a healthy lattice; duration f32 [B, U]: expected number of frames the
     label occupies); an utterance with no feasible alignment has -1 / 0 / 0 in every entry (include/ttmi.h, ttmi_ctc_emit_stats)"""
     _need_cuda(workspace, labels, act_lens, label_lens)
-    if labels.dim() != 2 or labels.shape[0] != B or labels.dtype is not torch.int32 or (labels.numel() and not labels.is_contiguous()):
-        raise ValueError("ctc: labels must be contiguous int32 [B, U]")
-    U = labels.shape[1]
+    U = _ctc_labels(labels, B)
     _trace("ctc_emit_stats", B, T, U)
     expected, mass, duration = (torch.empty(B, U, dtype=torch.float32, device=workspace.device) for _ in range(3))
     check(lib().ttmi_ctc_emit_stats(_p(workspace), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U), c_int(V),
@@ -595,10 +640,8 @@ def attn_fwd(x, p, mask, prec, p_drop=0.0, seed=0):
     B, L, d = x.shape
     K, H, Dh = p["r_emb"].shape
     L_ = lib()
-    L_.ttmi_attn_ctx_floats.restype = ctypes.c_size_t
-    L_.ttmi_attn_ws_floats.restype = ctypes.c_size_t
-    ctx = _f32(L_.ttmi_attn_ctx_floats(c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(prec)), x.device)
-    ws = scratch(L_.ttmi_attn_ws_floats(c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(prec)), x.device)
+    ctx = _f32(_sized("ttmi_attn_ctx_floats", c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(prec)), x.device)
+    ws = scratch(_sized("ttmi_attn_ws_floats", c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(prec)), x.device)
     y = torch.empty_like(x)
     check(L_.ttmi_attn_fwd(_p(x), _p(p["qkv_w"]), _p(p["o_w"]), _p(p["ln_g"]), _p(p["ln_b"]), _p(p["r_emb"]),
                            _p(p["r_w_bias"]), _p(p["r_bias"]), c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(K),
@@ -614,12 +657,10 @@ def attn_bwd(dy, x, p, ctx, prec, grads, p_drop=0.0, seed=0, mask=None, defer=No
     B, L, d = x.shape
     K, H, Dh = p["r_emb"].shape
     L_ = lib()
-    L_.ttmi_attn_ws_floats.restype = ctypes.c_size_t
-    ws = scratch(L_.ttmi_attn_ws_floats(c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(prec)), x.device)
+    ws = scratch(_sized("ttmi_attn_ws_floats", c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(prec)), x.device)
     dx = torch.empty_like(x)
     if defer is not None:
-        L_.ttmi_attn_bwd_keep_bytes.restype = ctypes.c_size_t
-        keep = torch.empty(L_.ttmi_attn_bwd_keep_bytes(c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh)), dtype=torch.uint8, device=x.device)
+        keep = torch.empty(_sized("ttmi_attn_bwd_keep_bytes", c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh)), dtype=torch.uint8, device=x.device)
         out = (WgradDesc * 2)()
         check(L_.ttmi_attn_bwd_defer(_p(dy), _p(x), _p(p["qkv_w"]), _p(p["o_w"]), _p(p["ln_g"]), _p(p["r_emb"]), _p(p["r_w_bias"]), _p(p["r_bias"]),
                                      c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(K), *(mask or MaskSpec()).args(), c_int(prec),
@@ -641,10 +682,8 @@ def ffn_fwd(y, p, prec, p_drop=0.0, p_layer=0.0, seed=0):
     rows, d = y.numel() // y.shape[-1], y.shape[-1]
     Di = p["ff_w1"].shape[0]
     L_ = lib()
-    L_.ttmi_ffn_ctx_floats.restype = ctypes.c_size_t
-    L_.ttmi_ffn_ws_floats.restype = ctypes.c_size_t
-    ctx = _f32(L_.ttmi_ffn_ctx_floats(c_long(rows), c_int(d), c_int(Di), c_int(prec)), y.device)
-    ws = scratch(L_.ttmi_ffn_ws_floats(c_long(rows), c_int(d), c_int(Di), c_int(prec)), y.device)
+    ctx = _f32(_sized("ttmi_ffn_ctx_floats", c_long(rows), c_int(d), c_int(Di), c_int(prec)), y.device)
+    ws = scratch(_sized("ttmi_ffn_ws_floats", c_long(rows), c_int(d), c_int(Di), c_int(prec)), y.device)
     z = torch.empty_like(y)
     check(L_.ttmi_ffn_fwd(_p(y), _p(p["ff_w1"]), _p(p["ff_b1"]), _p(p["ff_w2"]), _p(p["ff_b2"]), _p(p["ff_ln_g"]),
                           _p(p["ff_ln_b"]), c_long(rows), c_int(d), c_int(Di), c_int(prec), c_float(p_drop), c_float(p_layer),
@@ -658,12 +697,10 @@ def ffn_bwd(dz, y, p, ctx, prec, grads, p_drop=0.0, p_layer=0.0, seed=0, defer=N
     rows, d = y.numel() // y.shape[-1], y.shape[-1]
     Di = p["ff_w1"].shape[0]
     L_ = lib()
-    L_.ttmi_ffn_ws_floats.restype = ctypes.c_size_t
-    ws = scratch(L_.ttmi_ffn_ws_floats(c_long(rows), c_int(d), c_int(Di), c_int(prec)), y.device)
+    ws = scratch(_sized("ttmi_ffn_ws_floats", c_long(rows), c_int(d), c_int(Di), c_int(prec)), y.device)
     dy = torch.empty_like(y)
     if defer is not None:
-        L_.ttmi_ffn_bwd_keep_bytes.restype = ctypes.c_size_t
-        keep = torch.empty(L_.ttmi_ffn_bwd_keep_bytes(c_long(rows), c_int(d), c_int(Di)), dtype=torch.uint8, device=y.device)
+        keep = torch.empty(_sized("ttmi_ffn_bwd_keep_bytes", c_long(rows), c_int(d), c_int(Di)), dtype=torch.uint8, device=y.device)
         out = (WgradDesc * 2)()
         check(L_.ttmi_ffn_bwd_defer(_p(dz), _p(y), _p(p["ff_w1"]), _p(p["ff_w2"]), _p(p["ff_ln_g"]), c_long(rows), c_int(d), c_int(Di),
                                     c_int(prec), c_float(p_drop), c_float(p_layer), ctypes.c_uint(seed), _p(ctx), _p(ws), _p(dy),
@@ -682,9 +719,8 @@ def layer_fused(d, H, Dh, Di, prec):
     return bool(lib().ttmi_layer_fused(c_int(d), c_int(H), c_int(Dh), c_int(Di), c_int(prec)))
 
 
-def _layer_ws(L_, B, L, d, H, Dh, Di, prec, device):
-    L_.ttmi_layer_ws_floats.restype = ctypes.c_size_t
-    return scratch(L_.ttmi_layer_ws_floats(c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(Di), c_int(prec)), device)
+def _layer_ws(B, L, d, H, Dh, Di, prec, device):
+    return scratch(_sized("ttmi_layer_ws_floats", c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(Di), c_int(prec)), device)
 
 
 def layer_fwd(x, x16, pa, pf, mask, prec, p_attn=0.0, seed_attn=0, p_ffn=0.0, p_layer=0.0, seed_ffn=0, want16=False):
@@ -696,11 +732,9 @@ def layer_fwd(x, x16, pa, pf, mask, prec, p_attn=0.0, seed_attn=0, p_ffn=0.0, p_
     K, H, Dh = pa["r_emb"].shape
     Di = pf["ff_w1"].shape[0]
     L_ = lib()
-    L_.ttmi_attn_ctx_floats.restype = ctypes.c_size_t
-    L_.ttmi_ffn_ctx_floats.restype = ctypes.c_size_t
-    ctx_a = _f32(L_.ttmi_attn_ctx_floats(c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(prec)), x.device)
-    ctx_f = _f32(L_.ttmi_ffn_ctx_floats(c_long(B * L), c_int(d), c_int(Di), c_int(prec)), x.device)
-    ws = _layer_ws(L_, B, L, d, H, Dh, Di, prec, x.device)
+    ctx_a = _f32(_sized("ttmi_attn_ctx_floats", c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh), c_int(prec)), x.device)
+    ctx_f = _f32(_sized("ttmi_ffn_ctx_floats", c_long(B * L), c_int(d), c_int(Di), c_int(prec)), x.device)
+    ws = _layer_ws(B, L, d, H, Dh, Di, prec, x.device)
     y, z = torch.empty_like(x), torch.empty_like(x)
     z16 = torch.empty(x.shape, dtype=torch.bfloat16, device=x.device) if want16 else None
     check(L_.ttmi_layer_fwd(_p(x), _p(x16), _p(pa["qkv_w"]), _p(pa["o_w"]), _p(pa["ln_g"]), _p(pa["ln_b"]), _p(pa["r_emb"]), _p(pa["r_w_bias"]),
@@ -719,14 +753,12 @@ def layer_bwd(dz, x, x16, y, pa, pf, ctx_a, ctx_f, prec, grads, mask=None, p_att
     K, H, Dh = pa["r_emb"].shape
     Di = pf["ff_w1"].shape[0]
     L_ = lib()
-    ws = _layer_ws(L_, B, L, d, H, Dh, Di, prec, x.device)
+    ws = _layer_ws(B, L, d, H, Dh, Di, prec, x.device)
     dx = torch.empty_like(x)
     keep_a = keep_f = out = None
     if defer is not None:
-        L_.ttmi_attn_bwd_keep_bytes.restype = ctypes.c_size_t
-        L_.ttmi_ffn_bwd_keep_bytes.restype = ctypes.c_size_t
-        keep_a = torch.empty(L_.ttmi_attn_bwd_keep_bytes(c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh)), dtype=torch.uint8, device=x.device)
-        keep_f = torch.empty(L_.ttmi_ffn_bwd_keep_bytes(c_long(B * L), c_int(d), c_int(Di)), dtype=torch.uint8, device=x.device)
+        keep_a = torch.empty(_sized("ttmi_attn_bwd_keep_bytes", c_int(B), c_int(L), c_int(d), c_int(H), c_int(Dh)), dtype=torch.uint8, device=x.device)
+        keep_f = torch.empty(_sized("ttmi_ffn_bwd_keep_bytes", c_long(B * L), c_int(d), c_int(Di)), dtype=torch.uint8, device=x.device)
         out = (WgradDesc * 4)()
     for nm, t in (("dz", dz), ("x", x), ("y", y), ("ctx_attn", ctx_a), ("ctx_ffn", ctx_f), ("ws", ws), ("dx", dx)):
         if t is None or t.data_ptr() == 0:      # (round 6: one bench run in ~40 died here with the library's anonymous "null pointer"; name the tensor next time)
@@ -754,10 +786,8 @@ def joint_fwd(enc, dec, wf, bf, wp, bp, prec):
     U1, dd = dec.shape[1], dec.shape[2]
     J, V = wf.shape[0], wp.shape[0]
     L_ = lib()
-    L_.ttmi_joint_ctx_floats_prec.restype = ctypes.c_size_t
-    L_.ttmi_joint_ws_floats_prec.restype = ctypes.c_size_t
-    ctx = _f32(L_.ttmi_joint_ctx_floats_prec(c_int(B), c_int(T), c_int(U1), c_int(J), c_int(prec)), enc.device)
-    ws = scratch(L_.ttmi_joint_ws_floats_prec(c_int(B), c_int(T), c_int(U1), c_int(J), c_int(V), c_int(prec)), enc.device)
+    ctx = _f32(_sized("ttmi_joint_ctx_floats_prec", c_int(B), c_int(T), c_int(U1), c_int(J), c_int(prec)), enc.device)
+    ws = scratch(_sized("ttmi_joint_ws_floats_prec", c_int(B), c_int(T), c_int(U1), c_int(J), c_int(V), c_int(prec)), enc.device)
     dt = joint_logits_dtype(prec, J)
     # (f32 logits too: rows of V = 4334 floats start 8 bytes off every second time - the projection's epilogue then stores float by float, 12 of
     # the bf16x3 mode's 21 ms forward GEMM at C2; on a pitch of roundup(V, 64) every row piece is whole 16-byte stores.  The loss and its
@@ -776,8 +806,7 @@ def joint_bwd(dlogits, enc, dec, wf, wp, ctx, prec, grads, out=None):
     U1, dd = dec.shape[1], dec.shape[2]
     J, V = wf.shape[0], wp.shape[0]
     L_ = lib()
-    L_.ttmi_joint_ws_floats_prec.restype = ctypes.c_size_t
-    ws = scratch(L_.ttmi_joint_ws_floats_prec(c_int(B), c_int(T), c_int(U1), c_int(J), c_int(V), c_int(prec)), enc.device)
+    ws = scratch(_sized("ttmi_joint_ws_floats_prec", c_int(B), c_int(T), c_int(U1), c_int(J), c_int(V), c_int(prec)), enc.device)
     dt = joint_logits_dtype(prec, J)
     ldg = row_pitch(dlogits)
     if dt is torch.bfloat16:
@@ -829,8 +858,7 @@ def joint_bwd_split(planes, enc, dec, wf, wp, ctx, prec, grads, out=None):
     U1, dd = dec.shape[1], dec.shape[2]
     J, V = wf.shape[0], wp.shape[0]
     L_ = lib()
-    L_.ttmi_joint_ws_floats_prec.restype = ctypes.c_size_t
-    ws = scratch(L_.ttmi_joint_ws_floats_prec(c_int(B), c_int(T), c_int(U1), c_int(J), c_int(V), c_int(prec)), enc.device)
+    ws = scratch(_sized("ttmi_joint_ws_floats_prec", c_int(B), c_int(T), c_int(U1), c_int(J), c_int(V), c_int(prec)), enc.device)
     denc, ddec = (torch.empty_like(enc), torch.empty_like(dec)) if out is None else out
     assert denc.is_contiguous() and ddec.is_contiguous() and denc.shape == enc.shape and ddec.shape == dec.shape
     check(L_.ttmi_joint_bwd_split(_p(planes), c_long(row_pitch(planes)), _p(enc), _p(dec), _p(wf), _p(wp), c_int(B), c_int(T), c_int(U1), c_int(de),
@@ -847,9 +875,7 @@ def joint_exp_supported(B, T, U1, J, V, prec, fwd_only=False):
 
 
 def exp_padded_rows(B, T, U1):
-    f = lib().ttmi_joint_exp_padded_rows
-    f.restype = c_long
-    return int(f(c_int(B), c_int(T), c_int(U1)))
+    return int(_sized("ttmi_joint_exp_padded_rows", c_int(B), c_int(T), c_int(U1), restype=c_long))
 
 
 def joint_fwd_exp(enc, dec, wf, bf, wp, bp, prec, shift=None, labels=None, blank=0):
@@ -860,10 +886,8 @@ def joint_fwd_exp(enc, dec, wf, bf, wp, bp, prec, shift=None, labels=None, blank
     U1, dd = dec.shape[1], dec.shape[2]
     J, V = wf.shape[0], wp.shape[0]
     L_ = lib()
-    L_.ttmi_joint_ctx_floats_prec.restype = ctypes.c_size_t
-    L_.ttmi_joint_ws_floats_prec.restype = ctypes.c_size_t
-    ctx = _f32(L_.ttmi_joint_ctx_floats_prec(c_int(B), c_int(T), c_int(U1), c_int(J), c_int(prec)), enc.device)
-    ws = scratch(L_.ttmi_joint_ws_floats_prec(c_int(B), c_int(T), c_int(U1), c_int(J), c_int(V), c_int(prec)), enc.device)
+    ctx = _f32(_sized("ttmi_joint_ctx_floats_prec", c_int(B), c_int(T), c_int(U1), c_int(J), c_int(prec)), enc.device)
+    ws = scratch(_sized("ttmi_joint_ws_floats_prec", c_int(B), c_int(T), c_int(U1), c_int(J), c_int(V), c_int(prec)), enc.device)
     # room for the lattice rows padded to the wgrad's 64-row reduction tile (ttmi_joint_bwd_exp zero-fills the pad rows: include/ttmi.h)
     rows, ldv = B * T * U1, (V + 63) // 64 * 64
     rows_p = exp_padded_rows(B, T, U1)
@@ -900,34 +924,6 @@ def rnnt_shift_seed(workspace, act_lens, label_lens, B, T, U1, shift_next):
           "ttmi_rnnt_shift_seed")
 
 
-def rnnt_align(workspace, act_lens, label_lens, B, T, U1):
-    """best path through the lattice a finished rnnt_loss_fwd / rnnt_loss_fwd_exp left in `workspace` (read only) ->
-    (frames int32 [B, U1-1]: the frame at which label u+1 is emitted, -1 for u >= U_b; score f32 [B]: the path's log-probability).
-    The label move is taken only when strictly greater (a tie goes to blank); include/ttmi.h, ttmi_rnnt_align"""
-    _need_cuda(workspace, act_lens, label_lens)
-    _trace("rnnt_align", B, T, U1)
-    f = lib().ttmi_rnnt_align_workspace_bytes
-    f.restype = ctypes.c_size_t
-    aws = torch.empty((f(c_int(B), c_int(T), c_int(U1)) + 7) // 8, dtype=torch.int64, device=workspace.device)
-    frames = torch.empty(B, U1 - 1, dtype=torch.int32, device=workspace.device)
-    score = torch.empty(B, dtype=torch.float32, device=workspace.device)
-    check(lib().ttmi_rnnt_align(_p(workspace), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U1), _p(aws), _p(frames), _p(score),
-                                _stream()), "ttmi_rnnt_align")
-    return frames, score
-
-
-def rnnt_emit_stats(workspace, act_lens, label_lens, B, T, U1):
-    """per label, from the alpha / beta of a finished forward in `workspace` (read only) -> (expected f32 [B, U1-1]: expected emission frame,
-    -1 for u >= U_b; mass f32 [B, U1-1]: total emission posterior, 1 for a healthy lattice, 0 for u >= U_b)"""
-    _need_cuda(workspace, act_lens, label_lens)
-    _trace("rnnt_emit_stats", B, T, U1)
-    expected = torch.empty(B, U1 - 1, dtype=torch.float32, device=workspace.device)
-    mass = torch.empty(B, U1 - 1, dtype=torch.float32, device=workspace.device)
-    check(lib().ttmi_rnnt_emit_stats(_p(workspace), _p(act_lens), _p(label_lens), c_int(B), c_int(T), c_int(U1), _p(expected), _p(mass),
-                                     _stream()), "ttmi_rnnt_emit_stats")
-    return expected, mass
-
-
 def rnnt_loss_bwd_exp(P, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, fastemit_lambda=0.0):
     """patches P in place -> (srow f32 [rows], srow16 bf16 [rows]): d logits = srow[r] * P[r, :]"""
     fe = check_fastemit(fastemit_lambda)
@@ -946,8 +942,7 @@ def joint_bwd_exp(P, srow, srow16, enc, dec, wf, wp, ctx, prec, grads, out=None)
     U1, dd = dec.shape[1], dec.shape[2]
     J, V = wf.shape[0], wp.shape[0]
     L_ = lib()
-    L_.ttmi_joint_ws_floats.restype = ctypes.c_size_t
-    ws = scratch(L_.ttmi_joint_ws_floats(c_int(B), c_int(T), c_int(U1), c_int(J), c_int(V)), enc.device)
+    ws = scratch(_sized("ttmi_joint_ws_floats", c_int(B), c_int(T), c_int(U1), c_int(J), c_int(V)), enc.device)
     denc, ddec = (torch.empty_like(enc), torch.empty_like(dec)) if out is None else out
     assert denc.is_contiguous() and ddec.is_contiguous() and denc.shape == enc.shape and ddec.shape == dec.shape
     check(L_.ttmi_joint_bwd_exp(_p(P), c_long(row_pitch(P)), _p(srow), _p(srow16), _p(enc), _p(dec), _p(wf), _p(wp), c_int(B),
@@ -1006,9 +1001,7 @@ def probe_arm(slot=0):
 
 def probe_read_ms(slot=0, point=0):
     """duration of probe `point` (0 joint projection, 1 RNN-T loss forward, 2 RNN-T loss backward) armed in `slot`; < 0 = never fired"""
-    f = lib().ttmi_probe_point_read_ms
-    f.restype = ctypes.c_float
-    return float(f(c_int(point), c_int(slot)))
+    return float(_sized("ttmi_probe_point_read_ms", c_int(point), c_int(slot), restype=ctypes.c_float))
 
 
 # ----------------------------------------------------------------------------- throughput bf16 GEMMs (tests / tools)
@@ -1186,9 +1179,7 @@ def beam_step(logits, t, T_len, beam_in, beam_out, parent, fresh, blank=0):
 
 def beam_ctx_workspace(B, W, V, device):
     """the workspace of beam_step_ctx for [B, W, V] logits (ttmi_beam_ctx_ws_bytes): allocate once per decoding run, nothing is kept in it"""
-    f = lib().ttmi_beam_ctx_ws_bytes
-    f.restype = ctypes.c_size_t
-    return torch.empty(f(c_int(B), c_int(W), c_int(V)), dtype=torch.uint8, device=device)
+    return torch.empty(_sized("ttmi_beam_ctx_ws_bytes", c_int(B), c_int(W), c_int(V)), dtype=torch.uint8, device=device)
 
 
 def beam_step_ctx(logits, t, T_len, beam_in, beam_out, parent, fresh, tables, ctx_in, ctx_out, ws, blank=0):
@@ -1221,9 +1212,8 @@ def beam_step_ctx(logits, t, T_len, beam_in, beam_out, parent, fresh, tables, ct
     for state, bias in (ctx_in, ctx_out):
         assert state.dtype is torch.int32 and state.is_contiguous() and tuple(state.shape) == (B, W)
         assert bias.dtype is torch.float64 and bias.is_contiguous() and tuple(bias.shape) == (B, W)
-    f = lib().ttmi_beam_ctx_ws_bytes
-    f.restype = ctypes.c_size_t
-    assert ws.is_contiguous() and ws.numel() * ws.element_size() >= f(c_int(B), c_int(W), c_int(V)) and ws.data_ptr() % 8 == 0
+    assert (ws.is_contiguous() and ws.numel() * ws.element_size() >= _sized("ttmi_beam_ctx_ws_bytes", c_int(B), c_int(W), c_int(V)) and
+            ws.data_ptr() % 8 == 0)
     check(lib().ttmi_beam_step_ctx(_p(logits), c_int(_DT[logits.dtype]), c_long(logits.stride(-2)), c_int(B), c_int(W), c_int(V), c_int(blank),
                                    _p(t), _p(T_len), _p(s0), _p(n0), _p(h0), _p(f0), _p(l0), _p(s1), _p(n1), _p(h1), _p(f1), _p(l1),
                                    c_long(h0.shape[2]), c_long(f0.shape[2] if f0 is not None else 0), _p(parent), _p(fresh), c_int(S), c_int(A),
@@ -1236,9 +1226,7 @@ BEAM_FUSE_NORMS = {"logprob": 0, "softmax": 1, "softmax_no_blank": 2}
 
 def beam_fuse_workspace(B, W, V, device):
     """the workspace of beam_step_fuse for [B, W, V] logits (ttmi_beam_fuse_ws_bytes): allocate once per decoding run, nothing is kept in it"""
-    f = lib().ttmi_beam_fuse_ws_bytes
-    f.restype = ctypes.c_size_t
-    return torch.empty(f(c_int(B), c_int(W), c_int(V)), dtype=torch.uint8, device=device)
+    return torch.empty(_sized("ttmi_beam_fuse_ws_bytes", c_int(B), c_int(W), c_int(V)), dtype=torch.uint8, device=device)
 
 
 def beam_step_fuse(logits, t, T_len, beam_in, beam_out, parent, fresh, tables, ctx_in, ctx_out, ws, fuse_in, fuse_out, sources=(),
@@ -1280,9 +1268,8 @@ def beam_step_fuse(logits, t, T_len, beam_in, beam_out, parent, fresh, tables, c
         assert bias.dtype is torch.float64 and bias.is_contiguous() and tuple(bias.shape) == (B, W)
     for x in (fuse_in, fuse_out):
         assert x.dtype is torch.float64 and x.is_contiguous() and tuple(x.shape) == (B, W)
-    f = lib().ttmi_beam_fuse_ws_bytes
-    f.restype = ctypes.c_size_t
-    assert ws.is_contiguous() and ws.numel() * ws.element_size() >= f(c_int(B), c_int(W), c_int(V)) and ws.data_ptr() % 8 == 0
+    assert (ws.is_contiguous() and ws.numel() * ws.element_size() >= _sized("ttmi_beam_fuse_ws_bytes", c_int(B), c_int(W), c_int(V)) and
+            ws.data_ptr() % 8 == 0)
     ext = []
     for src in sources + [None] * (2 - len(sources)):
         if src is None:

@@ -110,86 +110,47 @@ def check_lengths(labels, act_lens, label_lens, B, T, U1, check_max):
             raise ValueError("Output length mismatch")
 
 
-class _RNNTLossFn(torch.autograd.Function):
+class _LatticeLossFn(torch.autograd.Function):
+    """the loss of either lattice on materialised logits; lat: its ops.Lattice record"""
+
     @staticmethod
-    def forward(ctx, acts, labels, act_lens, label_lens, blank, reduction, fastemit_lambda=0.0):
+    def forward(ctx, acts, labels, act_lens, label_lens, blank, reduction, fastemit_lambda, lat):
         B, T, U1, _ = acts.shape
         acts_c = acts if ops.row_pitch(acts) is not None else acts.contiguous()     # row-padded views are consumed in place
-        ws = ops.rnnt_workspace(B, T, U1, acts.device)
-        costs = ops.rnnt_loss_fwd(acts_c, labels, act_lens, label_lens, blank, ws)
+        ws = lat.workspace(B, T, U1, acts.device)
+        costs = lat.loss_fwd(acts_c, labels, act_lens, label_lens, blank, ws)
         ctx.save_for_backward(acts_c, labels, act_lens, label_lens, ws)
-        ctx.blank, ctx.reduction, ctx.fastemit_lambda = blank, reduction, fastemit_lambda
-        if reduction == "none":
-            return costs
-        out = costs.sum().reshape(1)
-        return out / B if reduction == "mean" else out
+        ctx.blank, ctx.reduction, ctx.fastemit_lambda, ctx.lat = blank, reduction, fastemit_lambda, lat
+        return ops.reduce_costs(costs, reduction)
 
     @staticmethod
     def backward(ctx, grad_out):
         acts, labels, act_lens, label_lens, ws = ctx.saved_tensors
-        B = acts.shape[0]
-        go = grad_out.contiguous().float()
-        per_utt = ctx.reduction == "none"
-        scale = 1.0 / B if ctx.reduction == "mean" else 1.0
-        grad = ops.rnnt_loss_bwd(acts, labels, act_lens, label_lens, ctx.blank, ws, go, 1 if per_utt else 0, scale,
-                                 fastemit_lambda=ctx.fastemit_lambda)
-        return grad, None, None, None, None, None, None
+        grad = ctx.lat.loss_bwd(acts, labels, act_lens, label_lens, ctx.blank, ws, *ops.grad_out_args(grad_out, ctx.reduction, acts.shape[0]),
+                                **ctx.lat.fastemit_kw(ctx.fastemit_lambda))
+        return grad, None, None, None, None, None, None, None
 
 
 def rnnt_loss(acts, labels, act_lens, label_lens, blank=0, reduction="mean", check_lengths=None, *, fastemit_lambda=0.0, topology="rnnt"):
     fastemit_lambda = ops.check_fastemit(fastemit_lambda)
-    mono = ops.check_topology(topology, fastemit_lambda) == "monotonic"
+    lat = ops.lattice(topology, fastemit_lambda)
     if check_lengths is None:
         check_lengths = os.environ.get("TTMI_CHECK_LENGTHS", "1") != "0"
     if not acts.is_cuda:
         raise ValueError("RNNTLoss: acts must live on the GPU (the MI355X build has no CPU path)")
     labels, act_lens, label_lens = (t.to(acts.device) for t in (labels, act_lens, label_lens))
     _certify(acts, labels, act_lens, label_lens, check_lengths)      # (shape / dtype queries only: a DeferredLogits handle stays a handle)
-    if mono and check_lengths:
+    if lat.label_takes_frame and check_lengths:
         check_monotonic_lengths(act_lens, label_lens)
     fused = getattr(acts, "rnnt_loss", None)
-    if fused is not None and mono:
-        out = fused(labels, act_lens, label_lens, int(blank), reduction, topology="monotonic")
-        if out is not None:
-            return out
-        acts = acts.materialize()
-    elif fused is not None:
+    if fused is not None:
         # `acts` is the handle Transducer.forward returns in the bf16 pipeline (tt.model.DeferredLogits): joint + loss run as one fused op on
         # the encoder states it carries and the logits are never formed - train.py:51-53 as written, on the path of Transducer.loss
-        out = fused(labels, act_lens, label_lens, int(blank), reduction, fastemit_lambda=fastemit_lambda)
+        out = fused(labels, act_lens, label_lens, int(blank), reduction, fastemit_lambda=fastemit_lambda, topology=lat.name)
         if out is not None:
             return out
         acts = acts.materialize()           # (per-utterance costs with gradients, or a handle that was already used as a tensor)
-    if mono:
-        return _MonoLossFn.apply(acts, labels, act_lens, label_lens, int(blank), reduction)
-    return _RNNTLossFn.apply(acts, labels, act_lens, label_lens, int(blank), reduction, fastemit_lambda)
-
-
-class _MonoLossFn(torch.autograd.Function):
-    """_RNNTLossFn on the monotonic lattice (ttmi_mono_loss_fwd / _bwd)"""
-
-    @staticmethod
-    def forward(ctx, acts, labels, act_lens, label_lens, blank, reduction):
-        B, T, U1, _ = acts.shape
-        acts_c = acts if ops.row_pitch(acts) is not None else acts.contiguous()     # row-padded views are consumed in place
-        ws = ops.mono_workspace(B, T, U1, acts.device)
-        costs = ops.mono_loss_fwd(acts_c, labels, act_lens, label_lens, blank, ws)
-        ctx.save_for_backward(acts_c, labels, act_lens, label_lens, ws)
-        ctx.blank, ctx.reduction = blank, reduction
-        if reduction == "none":
-            return costs
-        out = costs.sum().reshape(1)
-        return out / B if reduction == "mean" else out
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        acts, labels, act_lens, label_lens, ws = ctx.saved_tensors
-        B = acts.shape[0]
-        go = grad_out.contiguous().float()
-        per_utt = ctx.reduction == "none"
-        scale = 1.0 / B if ctx.reduction == "mean" else 1.0
-        grad = ops.mono_loss_bwd(acts, labels, act_lens, label_lens, ctx.blank, ws, go, 1 if per_utt else 0, scale)
-        return grad, None, None, None, None, None
+    return _LatticeLossFn.apply(acts, labels, act_lens, label_lens, int(blank), reduction, fastemit_lambda, lat)
 
 
 class AlignResult(NamedTuple):
@@ -218,40 +179,29 @@ def rnnt_align(acts, labels, act_lens, label_lens, blank=0, check_lengths=None, 
     of RNNTLoss(topology='monotonic') and of the decoders (include/ttmi.h, ttmi_mono_align): `frames` is then STRICTLY increasing, `score`
     is comparable with the decoders' DecodeResult.score, and under check_lengths an utterance with more labels than frames is a
     ValueError."""
-    mono = ops.check_topology(topology) == "monotonic"
+    lat = ops.lattice(topology)
     if check_lengths is None:
         check_lengths = os.environ.get("TTMI_CHECK_LENGTHS", "1") != "0"
     labels, act_lens, label_lens = (t.to(acts.device) for t in (labels, act_lens, label_lens))
     _certify(acts, labels, act_lens, label_lens, check_lengths)
     if not acts.is_cuda:
         raise ValueError("rnnt_align: acts must live on the GPU (the MI355X build has no CPU path)")
-    if mono and check_lengths:
+    if lat.label_takes_frame and check_lengths:
         check_monotonic_lengths(act_lens, label_lens)
     with torch.no_grad():
         fused = getattr(acts, "rnnt_align", None)
         if fused is not None:
-            out = fused(labels, act_lens, label_lens, int(blank), stats=bool(stats), topology="monotonic") if mono else \
-                fused(labels, act_lens, label_lens, int(blank), stats=bool(stats))
+            out = fused(labels, act_lens, label_lens, int(blank), stats=bool(stats), topology=lat.name)
             if out is not None:
                 return out
             acts = acts.materialize()
         acts = acts.detach()
         B, T, U1, _ = acts.shape
         acts_c = acts if ops.row_pitch(acts) is not None else acts.contiguous()
-        if mono:
-            ws = ops.mono_workspace(B, T, U1, acts.device)
-            cost = ops.mono_loss_fwd(acts_c, labels, act_lens, label_lens, int(blank), ws)
-            frames, score = ops.mono_align(ws, act_lens, label_lens, B, T, U1)
-            expected = mass = None
-            if stats:
-                expected, mass = ops.mono_emit_stats(ws, act_lens, label_lens, B, T, U1)
-            return AlignResult(frames, score, cost, expected, mass)
-        ws = ops.rnnt_workspace(B, T, U1, acts.device)
-        cost = ops.rnnt_loss_fwd(acts_c, labels, act_lens, label_lens, int(blank), ws)
-        frames, score = ops.rnnt_align(ws, act_lens, label_lens, B, T, U1)
-        expected = mass = None
-        if stats:
-            expected, mass = ops.rnnt_emit_stats(ws, act_lens, label_lens, B, T, U1)
+        ws = lat.workspace(B, T, U1, acts.device)
+        cost = lat.loss_fwd(acts_c, labels, act_lens, label_lens, int(blank), ws)
+        frames, score = lat.align(ws, act_lens, label_lens, B, T, U1)
+        expected, mass = lat.emit_stats(ws, act_lens, label_lens, B, T, U1) if stats else (None, None)
     return AlignResult(frames, score, cost, expected, mass)
 
 
