@@ -571,6 +571,20 @@ int ttmi_beam_step_fuse(const void* logits, int dtype, long ld, int B, int W, in
                         void* ws, const double* fuse_in, double* fuse_out, double sym_bonus, const void* ext_0, int ext_0_dtype, long ext_0_ld,
                         double ext_0_w, int ext_0_norm, const void* ext_1, int ext_1_dtype, long ext_1_ld, double ext_1_w, int ext_1_norm,
                         void* stream);
+/* The stable prefix of a beam: what a search that is still running (ttmi.beam.BeamSearch, the streaming recogniser) may show or act on.
+ * In: one beam as ttmi_beam_step leaves it: score f64 [B, W], len i32 [B, W], hist i64 [B, W, ld_hist] with column 0 the start symbol.
+ * Out: stable i32 [B].  A slot is live iff its score is > -inf (NaN and -inf are empty, the beam step's rule).  stable[b] = the largest
+ * n >= 0 such that every live slot w has len[b][w] >= n and hist[b][w][1 + i] == hist[b][w0][1 + i] for all i < n, w0 the first live slot;
+ * 0 without a live slot.  len is read clamped to [0, ld_hist - 1]: no index leaves a row whatever len holds.
+ * Why the prefix is permanent: every slot of a new beam continues a slot of the old one (its parent's tokens, or those and one symbol more),
+ * and a merge joins two candidates that spell the same tokens.  So what all live slots share, all their descendants share: the count of an
+ * utterance never decreases from frame to frame, and the tokens it covers are those of every final hypothesis.
+ * One wave per utterance: lanes across token positions, a loop over the slots, a wave-wide minimum of the first mismatch.  Ordinary vector
+ * loads and one vector store of the result; no allocation, no host synchronisation, no memset node, no atomics: capturable in a HIP graph,
+ * and two runs give the same bits.
+ * rc < 0 with a ttmi_last_error text, before any launch, on a null pointer, W outside [1, 32], ld_hist < 1 or B < 0.  B = 0 succeeds and
+ * does nothing. */
+int ttmi_beam_stable_prefix(const double* score, const int* len, const long* hist, long ld_hist, int B, int W, int* stable, void* stream);
 
 /* ---- error counting (ttmi.metrics: evaluation, and the per-hypothesis error counts of minimum word error rate training).
  * ttmi_edit_distance: token edit distance of P (hypothesis, transcript) pairs with its substitution / deletion / insertion counts.  One wave

@@ -1703,6 +1703,10 @@ int ttmi_beam_step_fuse(const void* logits, int dtype, long ld, int B, int W, in
                           state_in, bias_in, state_out, bias_out, ws, fuse_in, fuse_out, sym_bonus, ext_0, ext_0_dtype, ext_0_ld, ext_0_w,
                           ext_0_norm, ext_1, ext_1_dtype, ext_1_ld, ext_1_w, ext_1_norm, static_cast<hipStream_t>(stream));
 }
+// what a streaming search may commit: the tokens every live hypothesis of a beam shares (ttmi.beam.BeamSearch.stable, ttmi.h)
+int ttmi_beam_stable_prefix(const double* score, const int* len, const long* hist, long ld_hist, int B, int W, int* stable, void* stream) {
+    return beam_stable_prefix(score, len, hist, ld_hist, B, W, stable, static_cast<hipStream_t>(stream));
+}
 
 // ------------------------------------------------------------------ embedding (tt/decoder.py:26,39)
 int ttmi_embed_fwd(const long* tokens, const float* W, long n, int d, int V, float* out, void* stream) {

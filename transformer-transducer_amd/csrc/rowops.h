@@ -135,6 +135,8 @@ int beam_step_fuse(const void* logits, int dtype, long ld, int B, int W, int V, 
                    const int* state_in, const double* bias_in, int* state_out, double* bias_out, void* ws, const double* fuse_in,
                    double* fuse_out, double sym_bonus, const void* ext_0, int ext_0_dtype, long ext_0_ld, double ext_0_w, int ext_0_norm,
                    const void* ext_1, int ext_1_dtype, long ext_1_ld, double ext_1_w, int ext_1_norm, hipStream_t st);
+// how many leading tokens every live slot of a beam shares, per utterance (ttmi.h: ttmi_beam_stable_prefix; the walk: rowops.hip)
+int beam_stable_prefix(const double* score, const int* len, const long* hist, long ld_hist, int B, int W, int* stable, hipStream_t st);
 // batched transpose to bf16: for z = z1*nz2+z2, dst[z][c][r] = src[z1*s1 + z2*s2 + r*ld + c] (r < R, c < C), dst pitch ldd >= R with
 // zero fill in [R, ldd), dst slab = C*ldd.  src_dtype 0 = f32, 1 = bf16.  Produces the K-major operands of the position products.
 int transpose_bf16_batched(const void* src, int src_dtype, long ld, int nz1, int nz2, long s1, long s2, int R, int C, bf16_t* dst,

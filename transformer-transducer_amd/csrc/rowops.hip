@@ -2148,6 +2148,63 @@ int beam_step_fuse(const void* logits, int dtype, long ld, int B, int W, int V, 
     return TTMI_OK;
 }
 
+// ---- the stable prefix of a beam (ttmi.h: ttmi_beam_stable_prefix): how many leading tokens every live slot of an utterance shares.  ONE WAVE
+// PER UTTERANCE, one wave per workgroup (nothing is shared: no LDS, no barrier).  The W scores and lengths are read by every lane (wave-uniform
+// words) into a mask of live slots, the first live slot w0 and the shortest clamped length `lim`: no prefix is longer than that.  Then lanes
+// across token positions, 64 at a time: lane l of a pass holds column 1 + i0 + l of w0's row and compares it with the same column of every
+// other live slot (W - 1 coalesced 512-byte reads per pass); the ballot of the lanes that found a difference gives the first mismatch of the
+// pass - the wave-wide minimum - and the walk ends there.  Column 1 + i with i < lim <= ld_hist - 1 lies inside the row whatever len holds.
+// Integers only, no atomics: two runs give the same bits.
+namespace {
+
+__global__ __launch_bounds__(64) void beam_stable_prefix_kernel(const double* __restrict__ score, const int* __restrict__ len,
+                                                                const long* __restrict__ hist, long ld_hist, int W, int* __restrict__ stable) {
+    const int lane = threadIdx.x;
+    const long b = blockIdx.x;
+    const double* s = score + b * W;
+    const int* n = len + b * W;
+    const long* h = hist + b * W * ld_hist;
+    const int cap = ld_hist - 1 < 0x7fffffffL ? (int)(ld_hist - 1) : 0x7fffffff;
+    unsigned live = 0;
+    int w0 = -1, lim = 0x7fffffff;
+    for (int w = 0; w < W; ++w) {
+        if (!(s[w] > -INFINITY)) continue;                    // -inf or NaN: an empty slot (the beam step's rule)
+        if (w0 < 0) w0 = w;
+        live |= 1u << w;
+        const int l = n[w];
+        lim = min(lim, l < 0 ? 0 : l > cap ? cap : l);
+    }
+    if (w0 < 0) lim = 0;
+    int first = lim;
+    for (int i0 = 0; i0 < lim; i0 += 64) {
+        const int i = i0 + lane;
+        bool differs = false;
+        if (i < lim) {
+            const long ref = h[w0 * ld_hist + 1 + i];
+            for (int w = w0 + 1; w < W; ++w)
+                if ((live >> w) & 1u) differs |= h[w * ld_hist + 1 + i] != ref;
+        }
+        const unsigned long long m = __ballot(differs);
+        if (m) {
+            first = i0 + __ffsll(m) - 1;
+            break;
+        }
+    }
+    if (lane == 0) stable[b] = first;
+}
+
+}  // namespace
+
+int beam_stable_prefix(const double* score, const int* len, const long* hist, long ld_hist, int B, int W, int* stable, hipStream_t st) {
+    TTMI_REQUIRE(score && len && hist && stable, "beam_stable_prefix: null pointer");
+    TTMI_REQUIRE(W >= 1 && W <= BEAM_MAX_W, "beam_stable_prefix: beam width %d outside [1, %d]", W, BEAM_MAX_W);
+    TTMI_REQUIRE(ld_hist >= 1 && B >= 0, "beam_stable_prefix: bad arguments (ld_hist = %ld, B = %d)", ld_hist, B);
+    if (B == 0) return TTMI_OK;
+    hipLaunchKernelGGL(beam_stable_prefix_kernel, dim3(B), dim3(64), 0, st, score, len, hist, ld_hist, W, stable);
+    TTMI_LAUNCH_CHECK("beam_stable_prefix_kernel");
+    return TTMI_OK;
+}
+
 int greedy_scan_batch(const void* logits, int dtype, long ld, int B, int n, int V, int blank, const int* t, const int* T_len, const int* need,
                       unsigned long long* key, hipStream_t st) {
     TTMI_REQUIRE(logits && t && T_len && need && key && B > 0 && n > 0 && V > 0 && ld >= V, "greedy_scan_batch: bad arguments");

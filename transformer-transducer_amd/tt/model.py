@@ -1348,7 +1348,8 @@ class Transducer(nn.Module):
         list is ordered by score + final_bias + lm_total.  `score` stays the model's log-probability.  return_lm=True appends the
         lm_totals to the return, as return_bias does the biases.  Hotwords and an n-gram automaton at once need a product automaton: one
         context= per call.  Without lm, ilm_weight and length_bonus the calls are the ones above, launch for launch.
-        Not built: a cache of label states for sequences seen on earlier frames, a captured graph of the loop, a streaming variant."""
+        The same search over frames that arrive in blocks: `beam_search_state` (ttmi.beam.BeamSearch; this loop stays beside it as it is).
+        Not built: a cache of label states for sequences seen on earlier frames, a captured graph of the loop."""
         if not enc_states.is_cuda:
             raise ValueError("beam_decode_batch: enc_states must live on the GPU (the MI355X build has no CPU path)")
         W = int(beam_width)
@@ -1503,6 +1504,18 @@ class Transducer(nn.Module):
             lms.append(lmt[:nbest])
         ret = (out,) + ((biases,) if return_bias else ()) + ((lms,) if return_lm else ())
         return ret if len(ret) > 1 else out
+
+    def beam_search_state(self, B, beam_width=4, context=None, lm=None, lm_weight=0.0, ilm_weight=0.0, length_bonus=0.0, history="full",
+                          max_history=40, capacity=None):
+        """`beam_decode_batch`'s search of B utterances as an object that takes the encoder frames in blocks -> ttmi.beam.BeamSearch:
+        advance(enc_frames [B, n, d], n_valid) as often as frames arrive, stable() = how many leading tokens of each utterance can no longer
+        change, partial() = the currently best hypothesis, finish(nbest, return_bias, return_lm) = what beam_decode_batch returns for the same
+        frames, bit for bit, however they were split.  context / lm / lm_weight / ilm_weight / length_bonus as there.  history = "full": the
+        label state of a hypothesis is decoder([start] + tokens) as there; "stream": the streaming recogniser's rule, decoder(the last
+        max_history tokens) without a leading start symbol.  capacity = the columns the history buffers start with (default 64; they grow)."""
+        from ttmi.beam import BeamSearch
+        return BeamSearch(self, B, beam_width, context=context, lm=lm, lm_weight=lm_weight, ilm_weight=ilm_weight, length_bonus=length_bonus,
+                          history=history, max_history=max_history, capacity=capacity)
 
     @torch.no_grad()
     def recognize_nbest(self, inputs, inputs_length=None, audio_mask=None, beam_width=4, nbest=None, context=None, return_bias=False, lm=None,

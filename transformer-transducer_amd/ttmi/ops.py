@@ -1287,6 +1287,23 @@ def beam_step_fuse(logits, t, T_len, beam_in, beam_out, parent, fresh, tables, c
                                     _stream()), "ttmi_beam_step_fuse")
 
 
+def beam_stable_prefix(score, n_tok, hist, out=None):
+    """one beam as beam_step leaves it (score f64 [B, W], len i32 [B, W], hist i64 [B, W, ld_hist]) -> stable i32 [B]: how many leading tokens
+    every live slot of the utterance shares (include/ttmi.h: ttmi_beam_stable_prefix, the rule and why the prefix is permanent are written
+    there).  Device only, no synchronisation; `out` = a buffer to write into."""
+    _need_cuda(score, n_tok, hist, out)
+    B, W = score.shape
+    assert score.dtype is torch.float64 and score.is_contiguous()
+    assert n_tok.dtype is torch.int32 and n_tok.is_contiguous() and tuple(n_tok.shape) == (B, W)
+    assert hist.dtype is torch.long and hist.is_contiguous() and tuple(hist.shape[:2]) == (B, W)
+    if out is None:
+        out = torch.empty(B, dtype=torch.int32, device=score.device)
+    assert out.dtype is torch.int32 and out.is_contiguous() and tuple(out.shape) == (B,)
+    check(lib().ttmi_beam_stable_prefix(_p(score), _p(n_tok), _p(hist), c_long(hist.shape[2]), c_int(B), c_int(W), _p(out), _stream()),
+          "ttmi_beam_stable_prefix")
+    return out
+
+
 # ----------------------------------------------------------------------------- error counting (ttmi.metrics)
 def edit_distance(hyp, hyp_len, ref, ref_len, ref_index=None):
     """hyp i32 [P, Lh] / ref i32 [R, Lr] (last stride 1, any row pitch), hyp_len i32 [P], ref_len i32 [R], ref_index i32 [P] or None

@@ -17,7 +17,20 @@ was emitted on, and log P(symbol) there) and `score` accumulates the log-probabi
 frame: blank's where nothing is emitted, the symbol's where one is - the decoder's own path, not a path of the RNN-T lattice; see
 tt.model.DecodeResult).  The values come from the scan's own pass over the logits (ttmi_greedy_scan_batch_lp) and ride on the one host read per
 scanned block.
+
+beam_width=W (1 .. 32): the windows are searched by the frame-synchronous beam search instead (ttmi.beam.BeamSearch under the label-history
+rule above, history="stream"), with `context` (hotword boosting), `lm` / `lm_weight` / `ilm_weight` / `length_bonus` (language-model fusion)
+as Transducer.beam_decode_batch takes them.  Window logic, `windows`, `pos` and the feature buffer are the greedy path's.  After a window
+that is not the last, `result` grows by the tokens every live hypothesis shares (BeamSearch.stable(): they can no longer change) and feed()
+returns those; `partial` holds the currently best hypothesis (the stable prefix and a tentative tail).  The last feed() takes finish():
+`nbest_results` (at most `nbest` DecodeResult, best first) with `biases` and `lm_totals` beside it, `result` = the tokens of the best, and
+the return is what lies beyond the stable prefix.  A stable token is never retracted: the feed() returns concatenate to `result`.  `breaks`
+follows the best hypothesis's frames by the greedy rule (15 or more frames without a symbol in front of a symbol that is not the first);
+details=True: `frames` / `logprobs` / `score` are the best hypothesis's, final after the last window.  beam_width=None (the default) is the
+greedy path, unchanged.
 """
+import math
+
 import torch
 
 from . import frontend, ops
@@ -28,7 +41,16 @@ class StreamingRecognizer:
     WIN_AUDIO, AUDIO_STEP = 15999, 15519             # samples (:53-54)
 
     def __init__(self, model, left_context=None, right_context=None, n_layer=None, n_mels=128, max_history=40, block=64,
-                 sample_rate=16000, details=False):
+                 sample_rate=16000, details=False, beam_width=None, nbest=None, context=None, lm=None, lm_weight=0.0, ilm_weight=0.0,
+                 length_bonus=0.0):
+        if beam_width is None:
+            if context is not None or lm is not None or nbest is not None or any(float(v) != 0.0 for v in (lm_weight, ilm_weight, length_bonus)):
+                raise ValueError("StreamingRecognizer: nbest, context, lm, lm_weight, ilm_weight and length_bonus need beam_width (the greedy "
+                                 "path, beam_width=None, has no use for them)")
+        elif not 1 <= int(beam_width) <= 32 or (nbest is not None and int(nbest) < 1):
+            raise ValueError("StreamingRecognizer: beam_width must be in [1, 32] and nbest >= 1, got %r and %r" % (beam_width, nbest))
+        self.beam_width = None if beam_width is None else int(beam_width)
+        self.nbest, self.beam_args = nbest, dict(context=context, lm=lm, lm_weight=lm_weight, ilm_weight=ilm_weight, length_bonus=length_bonus)
         enc = model.config.enc
         self.model = model
         self.left = enc.left_context if left_context is None else left_context
@@ -40,6 +62,8 @@ class StreamingRecognizer:
         self.details = bool(details)
         if self.details and self.device.type != "cuda":
             raise ValueError("StreamingRecognizer(details=True): the model must live on the GPU (the MI355X build has no CPU path)")
+        if self.beam_width is not None and self.device.type != "cuda":
+            raise ValueError("StreamingRecognizer(beam_width=%d): the model must live on the GPU (the MI355X build has no CPU path)" % self.beam_width)
         self.reset()
 
     def reset(self):
@@ -54,6 +78,11 @@ class StreamingRecognizer:
         self.blank_frame = 0
         if self.details:
             self.frames, self.logprobs, self.score = [], [], 0.0
+        self.search = None
+        if self.beam_width is not None:
+            self.partial, self.nbest_results, self.biases, self.lm_totals = [], None, None, None
+            self.search = self.model.beam_search_state(1, self.beam_width, history="stream", max_history=self.max_history, **self.beam_args)
+            return
         with torch.no_grad():
             self.dec_state = self.model.decoder(torch.zeros(1, 1, dtype=torch.long, device=d))[:, -1:, :]      # :113-115
 
@@ -84,7 +113,10 @@ class StreamingRecognizer:
             enc = self.model.encoder(win, MaskSpec(2, left=self.left, right=self.right))
             self.windows.append((start, self.total, left_frame, right_frame, enc))
             eff = enc[0, left_frame:-right_frame]                  # :177-179 verbatim: empty when right_frame == 0
-            self._greedy(eff, emitted)
+            if self.search is None:
+                self._greedy(eff, emitted)
+            else:
+                self._beam(eff, last, emitted)
             self.pos += eff.shape[0]
             keep = max(0, self.pos - self.left_len)                # rows in front of the next window's history are never read again
             self.sub, self.base = self.sub[keep - self.base:], keep
@@ -118,6 +150,28 @@ class StreamingRecognizer:
             self.dec_state = self.model.decoder(hist)[:, -1:, :]   # :197-203: history of at most 40 symbols, no leading blank
             self.blank_frame = 0
             t += row + 1
+
+    def _beam(self, eff, last, emitted):
+        """the window's frames through the beam search; commits what every live hypothesis shares, on the last window the best final one"""
+        self.search.advance(eff[None])
+        if last:
+            res, biases, lms = self.search.finish(nbest=self.nbest, return_bias=True, return_lm=True)
+            self.nbest_results, self.biases, self.lm_totals = res[0], biases[0], lms[0]
+            best = self.nbest_results[0]
+            n = len(best.tokens)
+        else:
+            n = self.search.stable()[0]
+            best = self.search.partial()[0]
+            if not best.score > -math.inf:
+                raise RuntimeError("streaming decode: the beam holds no hypothesis with a finite score (NaN logits?)")
+        tokens = list(best.tokens)
+        assert tokens[:len(self.result)] == self.result and n >= len(self.result), "a stable token changed"
+        emitted.extend(tokens[len(self.result):n])
+        self.result = tokens[:n]
+        self.partial = tokens
+        self.breaks = [i for i in range(1, len(tokens)) if best.frames[i] - best.frames[i - 1] - 1 >= 15]
+        if self.details:
+            self.frames, self.logprobs, self.score = list(best.frames), list(best.logprobs), best.score
 
     def _scan_lp(self, logits2d):
         """ops.greedy_scan's (row, tok) plus the block's log-probabilities, lp[2 r] = log P(blank), lp[2 r + 1] = log P(argmax) of row r: the
