@@ -270,6 +270,30 @@ int ttmi_ctc_align(const void* workspace /* filled by ttmi_ctc_loss_fwd on the s
 int ttmi_ctc_emit_stats(const void* workspace, const int* labels, const int* act_lens, const int* label_lens, int B, int T, int U, int V,
                         int blank, float* expected, float* mass, float* duration /* each [B,U] */, void* stream);
 
+/* ---- CTC log-likelihood of hypotheses (N-best rescoring with the auxiliary head; no reference counterpart) -------------------------------
+ * score f64 [P]: score[p] = log P_ctc(hyp[p] | logits[utt(p)]), the full sum over alignments, for P (hypothesis, utterance) pairs that SHARE
+ * the utterances' logits: nothing is expanded per hypothesis, no emission table and no alpha is stored.
+ * logits f32 [B, T, V], row pitch ldv >= V; act_lens i32 [B], clamped to [1, T].  hyp i64 [P, ld_hyp] (a beam's token histories go in as they
+ * are), tokens clamped to [0, V-1]; hyp_len i32 [P], clamped to [0, U], U <= 1023 and U <= ld_hyp.  utt i32 [P] = the utterance of pair p,
+ * clamped to [0, B-1]; utt = NULL: P must be a multiple of B and pair p belongs to utterance p / (P / B) (the beam's [B, W] layout).
+ * The rule is ttmi_ctc_loss_fwd's, term for term and in its order: l' built literally (a token equal to `blank` is one more blank state),
+ * lp(t, s) = max(-1e30, z[b,t,l'_s] - lse[b,t]) with the same row walk for lse, the alpha recursion above in fp64 with the same log-add-exp
+ * order, the s-2 move only when l'_s != blank and l'_s != l'_{s-2}; score[p] = logsumexp(alpha(T_b-1, S-1), alpha(T_b-1, S-2)).  float(-score[p])
+ * has the bits of costs[p] of a ttmi_ctc_loss_fwd on the gathered [P, T, V] batch when every gathered row keeps its address modulo 16 (the
+ * row walk adds a row up from its first 16-byte boundary: another phase, another order, another last bit); where that cost is +inf (no
+ * feasible alignment: fewer frames than tokens plus adjacent repeats) score[p] = -inf; a NaN stays a NaN.  A pair never affects another pair.
+ * Two launches: the log-sum-exp of every row t < T_b once per utterance into `workspace` (ttmi_ctc_score_ws_bytes(B, T) bytes, 16-byte
+ * aligned, contents undefined afterwards), then one workgroup per pair over all T_b frames (U + 1 <= 64: one wave).  No allocation, host
+ * synchronisation, memset node or atomics; capturable in a HIP graph; two runs give the same bits; whatever the arrays hold, no index leaves
+ * an array.  rc < 0 with a ttmi_last_error text, before any launch, on a null pointer (hyp may be null when U = 0; utt may be null), B, T or
+ * P < 1, V < 2, blank outside [0, V), U < 0, U > 1023 or U > ld_hyp, ldv < V, utt = NULL with P % B != 0, a workspace that is not 16-byte
+ * aligned or a score pointer that is not 8-byte aligned. */
+size_t ttmi_ctc_score_ws_bytes(int B, int T);
+int ttmi_ctc_score_hyps(const float* logits, long ldv, const int* act_lens, int B, int T, int V, int blank,
+                        const long* hyp /* i64 [P, ld_hyp] */, long ld_hyp, const int* hyp_len /* [P] */,
+                        const int* utt /* i32 [P] or NULL */, int P, int U,
+                        void* workspace, double* score /* f64 [P] */, void* stream);
+
 /* ---- monotonic RNN-T loss (Tripathi et al. 2019, "Monotonic RNN-T"; no reference counterpart) --------------------------------------------
  * The forward-backward over the lattice the decoders of this library walk (ttmi_greedy_*, ttmi_beam_step[_ctx]): every frame makes exactly
  * ONE decision, blank or one label, and the emitting frame is consumed - where the standard lattice above lets a label keep its frame.

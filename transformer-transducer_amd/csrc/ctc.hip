@@ -12,6 +12,9 @@
 //                         workload's U = 50) is one wave with no barrier in the walk; longer label sequences are several waves, the
 //                         cell that crosses a wave boundary goes through a double-buffered LDS slot, one barrier per frame.  Emission
 //                         rows are prefetched CTC_PF frames ahead into registers.  Frontier in fp64 (lattice.h: lae).
+//   ctc_score_kernel      the alpha walk alone for P (hypothesis, utterance) pairs (ttmi_ctc_score_hyps: N-best rescoring): no emission table,
+//                         no stored alpha; every thread gathers its symbol's logit CTC_PF frames ahead, the log-sum-exp comes from
+//                         ctc_lse_kernel<false> once per utterance.
 //   ctc_grad_kernel       HBM-bound: one wave per row reads the logits once and writes g * softmax once (in place allowed), then the
 //                         owners of the row's symbols overwrite their columns with g * (softmax - occupancy).  No atomics.
 //   ctc_greedy_kernel     per-frame argmax in the order of the transducer's greedy scans (rowops.h), repeats collapsed, blanks dropped.
@@ -72,7 +75,16 @@ __global__ __launch_bounds__(256) void ctc_link_kernel(const int* __restrict__ l
     }
 }
 
+// lp(t, s) from the symbol's logit and the row's log-sum-exp; clamped at NEG so that a -inf logit is a dead transition and not an inf - inf
+// in the log-add-exp (a NaN stays a NaN)
+__device__ __forceinline__ float ctc_emit(float z, float lse) {
+    const float v = z - lse;
+    return v < NEG ? NEG : v;
+}
+
 // ------------------------------------------------------------------ lse + gather
+// GATHER = false (ttmi_ctc_score_hyps): the log-sum-exp alone - labels, label_lens and lp are not touched
+template <bool GATHER>
 __global__ __launch_bounds__(CTC_ROW_WAVES * 64) void ctc_lse_kernel(
     const float* __restrict__ logits, long ldv, const int* __restrict__ labels, const int* __restrict__ act_lens,
     const int* __restrict__ label_lens, int B, int T, int U, int V, int blank, int vec_ok, float* __restrict__ lse,
@@ -82,21 +94,91 @@ __global__ __launch_bounds__(CTC_ROW_WAVES * 64) void ctc_lse_kernel(
     if (row >= (long)B * T) return;
     const int t = (int)(row % T);
     const int b = (int)(row / T);
-    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(label_lens[b], 0, U);
+    const int Tb = clampi(act_lens[b], 1, T);
     if (t >= Tb) return;
     const float* r = logits + row * ldv;
     float M, s;
     row_lse<float>(r, V, vec_ok, lane, M, s);
     const float l = M + __logf(s);
     if (lane == 0) lse[row] = l;
-    // the row's 2 U_b + 1 emission log-probs (the row is in cache: it has just been read); clamped at NEG so that a -inf logit is a dead
-    // transition and not an inf - inf in the log-add-exp (a NaN stays a NaN)
-    float* lpr = lp + row * ctc_sp(U);
-    const int S = 2 * Ub + 1;
-    for (int si = lane; si < S; si += 64) {
-        const int sym = (si & 1) ? clampi(labels[(long)b * U + (si >> 1)], 0, V - 1) : blank;
-        const float v = r[sym] - l;
-        lpr[si] = v < NEG ? NEG : v;
+    if constexpr (GATHER) {
+        // the row's 2 U_b + 1 emission log-probs (the row is in cache: it has just been read)
+        const int Ub = clampi(label_lens[b], 0, U);
+        float* lpr = lp + row * ctc_sp(U);
+        const int S = 2 * Ub + 1;
+        for (int si = lane; si < S; si += 64) {
+            const int sym = (si & 1) ? clampi(labels[(long)b * U + (si >> 1)], 0, V - 1) : blank;
+            lpr[si] = ctc_emit(r[sym], l);
+        }
+    }
+}
+
+// ------------------------------------------------------------------ hypothesis scorer: the alpha walk alone, emissions gathered from the logits
+// score[p] = log P_ctc(hyp[p] | logits[utt(p)]): the alpha half of ctc_alphabeta_kernel, term for term and in its order, in the same shape
+// (thread k owns the state pair (2k, 2k+1), "label k-1" by the one-lane DPP rotate, the double-buffered LDS slot across a wave boundary;
+// U + 1 <= 64: one wave, no barrier in the walk) - without the emission table and without storing alpha.  Each thread gathers its own
+// symbol's logit z[b, t, y_k] CTC_PF frames ahead; the blank column and lse[b, t] are the same address for the whole workgroup.  The pairs of
+// one utterance are neighbours in the grid: after its first hypothesis the utterance's rows come from cache.
+template <bool MULTI>
+__global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_score_kernel(
+    const float* __restrict__ logits, long ldv, const float* __restrict__ lse, const int* __restrict__ act_lens, int B, int T, int V,
+    int blank, const long* __restrict__ hyp, long ld_hyp, const int* __restrict__ hyp_len, const int* __restrict__ utt, int per, int U,
+    acc_t* __restrict__ score) {
+    __shared__ acc_t bnd[2][16];          // the label cell that crosses a wave boundary, double-buffered by frame parity
+    __shared__ acc_t fin;
+    const int p = blockIdx.x;
+    const int b = utt ? clampi(utt[p], 0, B - 1) : p / per;     // utt == NULL: P = B * per, the beam's [B, W] layout
+    const int k = threadIdx.x, lane = k & 63, wave = k >> 6;
+    const int Tb = clampi(act_lens[b], 1, T), Ub = clampi(hyp_len[p], 0, U);
+    const bool vb = k <= Ub, vl = k < Ub;             // this thread's blank / label state exists
+    const long* h = hyp + (long)p * ld_hyp;
+    auto tok = [&](int i) -> int {
+        const long v = h[i];
+        return (int)(v < 0 ? 0 : (v > V - 1 ? V - 1 : v));
+    };
+    const int yk = vl ? tok(k) : -1;
+    // skip transition into label state 2k+1 from 2k-1: l'_s != blank and l'_s != l'_{s-2}
+    const bool skip = vl && k > 0 && yk != blank && yk != tok(k > 0 ? k - 1 : 0);
+    const float* zr = logits + (long)b * T * ldv;
+    const float* ls = lse + (long)b * T;
+    const int col = vl ? yk : blank;                  // threads without a label state gather the blank column (in range, never used)
+    struct Em { float zb, zl, l; };                   // frame t as loaded: blank logit, own symbol's logit, log-sum-exp
+    auto load = [&](int t) -> Em { return Em{zr[(long)t * ldv + blank], zr[(long)t * ldv + col], ls[t]}; };
+    Em cur[CTC_PF], nxt[CTC_PF];
+    const Em e0 = load(0);
+    acc_t ab = k == 0 ? (acc_t)ctc_emit(e0.zb, e0.l) : (acc_t)NEG;
+    acc_t al = (k == 0 && vl) ? (acc_t)ctc_emit(e0.zl, e0.l) : (acc_t)NEG;
+#pragma unroll
+    for (int i = 0; i < CTC_PF; ++i) cur[i] = load(min(1 + i, Tb - 1));
+    for (int base = 1; base < Tb; base += CTC_PF) {
+#pragma unroll
+        for (int i = 0; i < CTC_PF; ++i) nxt[i] = load(min(base + CTC_PF + i, Tb - 1));
+#pragma unroll
+        for (int i = 0; i < CTC_PF; ++i) {
+            const int t = base + i;
+            if (t < Tb) {                              // workgroup-uniform
+                if (MULTI) {
+                    if (lane == 63) bnd[t & 1][wave] = al;
+                    __syncthreads();
+                }
+                acc_t nb = rot_r1(al);                 // label state of thread k-1 at frame t-1
+                if (lane == 0) nb = (MULTI && wave > 0) ? bnd[t & 1][wave > 0 ? wave - 1 : 0] : (acc_t)NEG;
+                acc_t ml = lae(al, ab);
+                if (skip) ml = lae(ml, nb);
+                const acc_t nab = vb ? (acc_t)ctc_emit(cur[i].zb, cur[i].l) + lae(ab, nb) : (acc_t)NEG;
+                al = vl ? (acc_t)ctc_emit(cur[i].zl, cur[i].l) + ml : (acc_t)NEG;
+                ab = nab;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < CTC_PF; ++i) cur[i] = nxt[i];
+    }
+    // logsumexp(alpha(T_b-1, 2 U_b), alpha(T_b-1, 2 U_b - 1)): thread U_b holds the first, thread U_b - 1 the second
+    if (Ub > 0 && k == Ub - 1) fin = al;
+    __syncthreads();
+    if (k == Ub) {
+        const acc_t v = Ub > 0 ? lae(ab, fin) : ab;
+        score[p] = v <= CTC_DEAD ? (acc_t)-INFINITY : v;            // no feasible alignment: -inf, the loss's +inf (a NaN stays a NaN)
     }
 }
 
@@ -589,7 +671,7 @@ int ttmi_ctc_loss_fwd(const float* logits, long ldv, const int* labels, const in
         hipLaunchKernelGGL(ctc_link_kernel, dim3(B), dim3(256), 0, st, labels, label_lens, U, V, blank, w.link);
         TTMI_LAUNCH_CHECK("ctc_link_kernel");
     }
-    hipLaunchKernelGGL(ctc_lse_kernel, dim3(cdiv(rows, CTC_ROW_WAVES)), dim3(CTC_ROW_WAVES * 64), 0, st, logits, ldv, labels, act_lens,
+    hipLaunchKernelGGL(ctc_lse_kernel<true>, dim3(cdiv(rows, CTC_ROW_WAVES)), dim3(CTC_ROW_WAVES * 64), 0, st, logits, ldv, labels, act_lens,
                        label_lens, B, T, U, V, blank, vec_ok, w.lse, w.lp);
     TTMI_LAUNCH_CHECK("ctc_lse_kernel");
     const int threads = cdiv(U + 1, 64) * 64;
@@ -621,6 +703,44 @@ int ttmi_ctc_loss_bwd(const float* logits, long ldv, const int* labels, const in
                        label_lens, B, T, U, V, blank, vec_ok, w.lse, w.lp, w.alpha, w.beta, w.ll, w.link, grad_out, grad_out_stride, scale,
                        grad, ldg);
     TTMI_LAUNCH_CHECK("ctc_grad_kernel");
+    return TTMI_OK;
+}
+
+// Full-sum CTC log-likelihood of P hypotheses on the logits of their utterances (include/ttmi.h): the log-sum-exp of every row once per
+// utterance into `workspace`, then one workgroup per pair.  No allocation, host synchronisation, memset node or atomics.
+size_t ttmi_ctc_score_ws_bytes(int B, int T) {
+    if (B <= 0 || T <= 0) return 0;
+    return (sizeof(float) * (size_t)B * T + 15) & ~(size_t)15;
+}
+
+int ttmi_ctc_score_hyps(const float* logits, long ldv, const int* act_lens, int B, int T, int V, int blank, const long* hyp, long ld_hyp,
+                        const int* hyp_len, const int* utt, int P, int U, void* workspace, double* score, void* stream) {
+    TTMI_REQUIRE(logits && act_lens && (hyp || U == 0) && hyp_len && workspace && score, "ctc_score_hyps: null pointer");
+    TTMI_REQUIRE(B > 0 && T > 0 && P > 0 && V >= 2, "ctc_score_hyps: bad shape B=%d T=%d P=%d V=%d", B, T, P, V);
+    TTMI_REQUIRE(U >= 0, "ctc_score_hyps: bad shape U=%d", U);
+    TTMI_REQUIRE(U <= 1023, "ctc_score_hyps: U=%d > 1023 unsupported", U);
+    TTMI_REQUIRE(U <= ld_hyp, "ctc_score_hyps: U=%d above the hypothesis pitch %ld", U, ld_hyp);
+    TTMI_REQUIRE(ldv >= V, "ctc_score_hyps: bad pitch");
+    TTMI_REQUIRE(blank >= 0 && blank < V, "ctc_score_hyps: blank %d outside [0,%d)", blank, V);
+    TTMI_REQUIRE(utt || P % B == 0, "ctc_score_hyps: without utt P=%d must be a multiple of B=%d", P, B);
+    TTMI_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "ctc_score_hyps: workspace must be 16-byte aligned");
+    TTMI_REQUIRE((reinterpret_cast<uintptr_t>(score) & 7) == 0, "ctc_score_hyps: score must be 8-byte aligned");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float* lse = static_cast<float*>(workspace);
+    const long rows = (long)B * T;
+    hipLaunchKernelGGL(ctc_lse_kernel<false>, dim3(cdiv(rows, CTC_ROW_WAVES)), dim3(CTC_ROW_WAVES * 64), 0, st, logits, ldv,
+                       static_cast<const int*>(nullptr), act_lens, static_cast<const int*>(nullptr), B, T, 0, V, blank, rows_vec_ok(logits, 4), lse,
+                       static_cast<float*>(nullptr));
+    TTMI_LAUNCH_CHECK("ctc_lse_kernel");
+    const int threads = cdiv(U + 1, 64) * 64;
+    const int per = utt ? 1 : P / B;
+    if (threads == 64)
+        hipLaunchKernelGGL(ctc_score_kernel<false>, dim3(P), dim3(64), 0, st, logits, ldv, lse, act_lens, B, T, V, blank, hyp, ld_hyp, hyp_len,
+                           utt, per, U, score);
+    else
+        hipLaunchKernelGGL(ctc_score_kernel<true>, dim3(P), dim3(threads), 0, st, logits, ldv, lse, act_lens, B, T, V, blank, hyp, ld_hyp,
+                           hyp_len, utt, per, U, score);
+    TTMI_LAUNCH_CHECK("ctc_score_kernel");
     return TTMI_OK;
 }
 

@@ -968,6 +968,17 @@ class Transducer(nn.Module):
             raise RuntimeError("ctc_loss_from_last_forward: no audio states kept (call the model first; one loss per forward)")
         return self._ctc_from_states(enc_state, targets, inputs_length, targets_length, reduction)
 
+    def _ctc_head_logits(self, enc_state):
+        """the CTC head on audio states [B, T, d] -> f32 logits [B, T, V], the [..., :V] view of a row-padded buffer (ops.linear_nt)"""
+        enc_state = enc_state.contiguous()
+        B, T, d = enc_state.shape
+        V = self.ctc_head.out_features
+        buf, logits = ops.padded_empty((B, T, V), torch.float32, enc_state.device)
+        ops.weights_fresh()
+        ops.linear_nt(enc_state.reshape(B * T, d), self.ctc_head.weight.detach(), buf.view(B * T, buf.shape[-1])[:, :V],
+                      bias=self.ctc_head.bias.detach(), prec=default_precision())
+        return logits
+
     @torch.no_grad()
     def recognize_ctc(self, inputs, inputs_length=None, audio_mask=None):
         """non-autoregressive recognition with the CTC head: per utterance the argmax of the head over its frames, repeats collapsed, blanks
@@ -977,15 +988,30 @@ class Transducer(nn.Module):
             raise ValueError("this Transducer has no CTC head: build it with config.ctc_weight > 0")
         if not inputs.is_cuda:
             raise ValueError("recognize_ctc: inputs must live on the GPU (the MI355X build has no CPU path)")
-        enc_state = self.encoder(inputs, self._audio_mask(inputs) if audio_mask is None else audio_mask).contiguous()
-        B, T, d = enc_state.shape
-        V = self.ctc_head.out_features
-        buf, logits = ops.padded_empty((B, T, V), torch.float32, enc_state.device)
-        ops.weights_fresh()
-        ops.linear_nt(enc_state.reshape(B * T, d), self.ctc_head.weight.detach(), buf.view(B * T, buf.shape[-1])[:, :V],
-                      bias=self.ctc_head.bias.detach(), prec=default_precision())
+        enc_state = self.encoder(inputs, self._audio_mask(inputs) if audio_mask is None else audio_mask)
+        logits = self._ctc_head_logits(enc_state)
         lens = None if inputs_length is None else torch.as_tensor(inputs_length).to(enc_state.device)
         return ctc_greedy_decode(logits, lens, blank=0)
+
+    @torch.no_grad()
+    def ctc_score(self, inputs, inputs_length, hypotheses, audio_mask=None):
+        """The CTC head's log-likelihood of given token sequences (blank = 0): the audio encoder once, the head as `recognize_ctc` forms it,
+        then ttmi.ctc.ctc_score, every hypothesis of an utterance on that utterance's logits.  hypotheses = per utterance a list of token
+        lists -> the same nesting of floats (-inf where the utterance has fewer frames than the hypothesis needs).  It is the term
+        `beam_decode_batch(ctc_weight=...)` adds to its ordering key.  ValueError on a module without the head."""
+        from ttmi.ctc import ctc_score
+        if getattr(self, "ctc_head", None) is None:
+            raise ValueError("this Transducer has no CTC head: build it with config.ctc_weight > 0")
+        if not inputs.is_cuda:
+            raise ValueError("Transducer.ctc_score: inputs must live on the GPU (the MI355X build has no CPU path)")
+        enc_state = self.encoder(inputs, self._audio_mask(inputs) if audio_mask is None else audio_mask)
+        lens = None if inputs_length is None else torch.as_tensor(inputs_length).to(enc_state.device)
+        flat = ctc_score(self._ctc_head_logits(enc_state), hypotheses, lens, blank=0).cpu().tolist()
+        out, i = [], 0
+        for hyps in hypotheses:
+            out.append(flat[i:i + len(hyps)])
+            i += len(hyps)
+        return out
 
     @torch.no_grad()
     def align_ctc(self, inputs, inputs_length, targets, targets_length, *, stats=False):
@@ -1000,13 +1026,7 @@ class Transducer(nn.Module):
             raise ValueError("this Transducer has no CTC head: build it with config.ctc_weight > 0")
         if not inputs.is_cuda:
             raise ValueError("Transducer.align_ctc: inputs must live on the GPU (the MI355X build has no CPU path)")
-        enc_state = self.encoder(inputs, self._audio_mask(inputs)).contiguous()
-        B, T, d = enc_state.shape
-        V = self.ctc_head.out_features
-        buf, logits = ops.padded_empty((B, T, V), torch.float32, enc_state.device)
-        ops.weights_fresh()
-        ops.linear_nt(enc_state.reshape(B * T, d), self.ctc_head.weight.detach(), buf.view(B * T, buf.shape[-1])[:, :V],
-                      bias=self.ctc_head.bias.detach(), prec=default_precision())
+        logits = self._ctc_head_logits(self.encoder(inputs, self._audio_mask(inputs)))
         return ctc_align(logits, targets, inputs_length, targets_length, blank=0, stats=stats)
 
     def align(self, inputs, inputs_length, targets, targets_length, chunk=None, check_lengths=True, exp_domain=False, *, stats=False):
@@ -1321,7 +1341,7 @@ class Transducer(nn.Module):
 
     @torch.no_grad()
     def beam_decode_batch(self, enc_states, lengths, beam_width=4, nbest=None, context=None, return_bias=False, lm=None, lm_weight=0.0,
-                          ilm_weight=0.0, length_bonus=0.0, return_lm=False):
+                          ilm_weight=0.0, length_bonus=0.0, return_lm=False, ctc_weight=0.0, return_ctc=False):
         """Frame-synchronous beam search of EVERY utterance of a batch at once -> per utterance a list of at most `nbest` (default: beam_width)
         DecodeResult, best first.  The probability model is the greedy decoder's (`decode_batch`): each of an utterance's T_b frames takes one
         decision, blank or one symbol, against the label state of the tokens so far, and the emitting frame is consumed.  Unlike `beam_search`
@@ -1348,6 +1368,15 @@ class Transducer(nn.Module):
         list is ordered by score + final_bias + lm_total.  `score` stays the model's log-probability.  return_lm=True appends the
         lm_totals to the return, as return_bias does the biases.  Hotwords and an n-gram automaton at once need a product automaton: one
         context= per call.  Without lm, ilm_weight and length_bonus the calls are the ones above, launch for launch.
+        ctc_weight > 0 (a model with the CTC head): joint CTC - transducer rescoring of the final beam.  The search itself is untouched; after
+        the last frame the head's logits are formed once from enc_states, ttmi_ctc_score_hyps gives ctc = the head's full-sum log-likelihood
+        of the tokens of every one of the B x W slots, read from the beam's own arrays, and each list is ordered by
+        score + final_bias + lm_total + ctc_weight * ctc (f64, added in that order), descending, the slot ascending on ties - before the cut
+        to `nbest`, so the head can promote a hypothesis from anywhere in the beam.  A hypothesis the head finds infeasible (ctc = -inf:
+        fewer frames than tokens plus adjacent repeats) or NaN comes after all others, in the order of the key without the CTC term, and
+        is still returned.  `score` stays the model's log-probability.  return_ctc=True appends ctcs[b][n] to the return, after biases
+        and lm_totals (with ctc_weight = 0 the values are computed and change no order).  With ctc_weight = 0 and return_ctc=False nothing
+        of this runs.  ValueError on a module without the head, or when max(lengths) > 1023 (the scorer's longest hypothesis).
         The same search over frames that arrive in blocks: `beam_search_state` (ttmi.beam.BeamSearch; this loop stays beside it as it is).
         Not built: a cache of label states for sequences seen on earlier frames, a captured graph of the loop."""
         if not enc_states.is_cuda:
@@ -1360,6 +1389,12 @@ class Transducer(nn.Module):
             if not math.isfinite(float(v)) or (name != "length_bonus" and float(v) < 0.0):
                 raise ValueError("beam_decode_batch: %s must be finite%s, got %r" % (name, "" if name == "length_bonus" else " and >= 0", v))
         lm_weight, ilm_weight, length_bonus = float(lm_weight), float(ilm_weight), float(length_bonus)
+        if not math.isfinite(float(ctc_weight)) or float(ctc_weight) < 0.0:
+            raise ValueError("beam_decode_batch: ctc_weight must be finite and >= 0, got %r" % (ctc_weight,))
+        ctc_weight = float(ctc_weight)
+        use_ctc = ctc_weight > 0.0 or bool(return_ctc)
+        if use_ctc and getattr(self, "ctc_head", None) is None:
+            raise ValueError("this Transducer has no CTC head: build it with config.ctc_weight > 0")
         fused = lm is not None or ilm_weight != 0.0 or length_bonus != 0.0
         if lm is not None:
             if lm.norm not in ops.BEAM_FUSE_NORMS:
@@ -1370,6 +1405,8 @@ class Transducer(nn.Module):
         B, T = enc_states.shape[0], enc_states.shape[1]
         lens = [T] * B if lengths is None else [min(int(v), T) for v in torch.as_tensor(lengths).tolist()]
         T_max = max(lens + [0])
+        if use_ctc and T_max > 1023:
+            raise ValueError("beam_decode_batch: CTC rescoring takes at most 1023 frames (the scorer's longest hypothesis), got %d" % T_max)
         T_len = torch.tensor(lens, dtype=torch.int32, device=dev)
         t = torch.zeros(B, dtype=torch.int32, device=dev)
         ld_hist, ld_det = T_max + 2, T_max + 1                       # at most one symbol per frame; column 0 = the start symbol (blank)
@@ -1478,11 +1515,18 @@ class Transducer(nn.Module):
             from ttmi.lm import eos_logprob
             lm_total = cur["fuse"] + lm_weight * eos_logprob(lm_rows, lm.norm, lm.eos) if need_eos else cur["fuse"]
             packed = torch.cat([packed, lm_total[:, :, None]], dim=2)
+        if use_ctc:
+            # the head's log-likelihood of every slot's tokens: the head once on the audio states, then all B x W slots in one call, each
+            # on its utterance's logits, straight from the beam's history and length arrays (an utterance has at most T_max tokens)
+            ctc = ops.ctc_score_hyps(self._ctc_head_logits(enc_states), T_len,
+                                     cur["hist"].view(B * W, ld_hist)[:, 1:1 + T_max], cur["meta"][0].reshape(B * W), None, blank=0)
+            packed = torch.cat([packed, ctc.view(B, W, 1)], dim=2)
         packed = packed.cpu()
-        bias_col = -1 - int(fused)
-        out, biases, lms = [], [], []
+        lm_col = -1 - int(use_ctc)
+        bias_col = lm_col - int(fused)
+        out, biases, lms, ctcs = [], [], [], []
         for b in range(B):
-            res, bias, lmt = [], [], []
+            res, bias, lmt, ctl = [], [], [], []
             for w in range(W):
                 score, c = float(packed[b, w, 0]), int(packed[b, w, 1])
                 if not score > -math.inf:                            # an empty slot
@@ -1490,19 +1534,25 @@ class Transducer(nn.Module):
                 tok, frm, lpr = (packed[b, w, 2 + i * ld_det:2 + i * ld_det + c].tolist() for i in range(3))
                 res.append(DecodeResult([int(v) for v in tok], [int(v) for v in frm], lpr, score))
                 bias.append(0.0 if context is None else float(packed[b, w, bias_col]))
-                lmt.append(float(packed[b, w, -1]) if fused else 0.0)
-            if fused:                                                # ... and so does the LM's closing term
+                lmt.append(float(packed[b, w, lm_col]) if fused else 0.0)
+                ctl.append(float(packed[b, w, -1]) if use_ctc else 0.0)
+            if ctc_weight > 0.0:                                     # the head's term joins the key; what it cannot align comes last
+                order = sorted(range(len(res)), key=lambda n: (0, -(res[n].score + bias[n] + lmt[n] + ctc_weight * ctl[n]), n) if math.isfinite(ctl[n])
+                               else (1, -(res[n].score + bias[n] + lmt[n]), n))
+                res, bias, lmt, ctl = ([v[n] for n in order] for v in (res, bias, lmt, ctl))
+            elif fused:                                              # ... and so does the LM's closing term
                 order = sorted(range(len(res)), key=lambda n: (-(res[n].score + bias[n] + lmt[n]), n))
-                res, bias, lmt = [res[n] for n in order], [bias[n] for n in order], [lmt[n] for n in order]
+                res, bias, lmt, ctl = ([v[n] for n in order] for v in (res, bias, lmt, ctl))
             elif context is not None:                                # the slots are in key order with the running bias; the final bias reorders
                 order = sorted(range(len(res)), key=lambda n: (-(res[n].score + bias[n]), n))
-                res, bias = [res[n] for n in order], [bias[n] for n in order]
+                res, bias, ctl = ([v[n] for n in order] for v in (res, bias, ctl))
             if not res or not math.isfinite(res[0].score):
                 raise RuntimeError("beam search: utterance %d has no hypothesis with a finite score (NaN logits?)" % b)
             out.append(res[:nbest])
             biases.append(bias[:nbest])
             lms.append(lmt[:nbest])
-        ret = (out,) + ((biases,) if return_bias else ()) + ((lms,) if return_lm else ())
+            ctcs.append(ctl[:nbest])
+        ret = (out,) + ((biases,) if return_bias else ()) + ((lms,) if return_lm else ()) + ((ctcs,) if return_ctc else ())
         return ret if len(ret) > 1 else out
 
     def beam_search_state(self, B, beam_width=4, context=None, lm=None, lm_weight=0.0, ilm_weight=0.0, length_bonus=0.0, history="full",
@@ -1519,15 +1569,17 @@ class Transducer(nn.Module):
 
     @torch.no_grad()
     def recognize_nbest(self, inputs, inputs_length=None, audio_mask=None, beam_width=4, nbest=None, context=None, return_bias=False, lm=None,
-                        lm_weight=0.0, ilm_weight=0.0, length_bonus=0.0, return_lm=False):
+                        lm_weight=0.0, ilm_weight=0.0, length_bonus=0.0, return_lm=False, ctc_weight=0.0, return_ctc=False):
         """N-best recognition of a batch: the encoder, then `beam_decode_batch` -> per utterance a list of at most `nbest` (default:
         beam_width) DecodeResult, best first, with merged, comparable scores; `context` / `return_bias`: contextual biasing, `lm` /
-        `lm_weight` / `ilm_weight` / `length_bonus` / `return_lm`: language-model fusion, see there"""
+        `lm_weight` / `ilm_weight` / `length_bonus` / `return_lm`: language-model fusion, `ctc_weight` / `return_ctc`: rescoring of the
+        final beam with the CTC head, see there"""
         if not inputs.is_cuda:
             raise ValueError("recognize_nbest: inputs must live on the GPU (the MI355X build has no CPU path)")
         enc_states = self.encoder(inputs, audio_mask)
         return self.beam_decode_batch(enc_states, inputs_length, beam_width=beam_width, nbest=nbest, context=context, return_bias=return_bias,
-                                      lm=lm, lm_weight=lm_weight, ilm_weight=ilm_weight, length_bonus=length_bonus, return_lm=return_lm)
+                                      lm=lm, lm_weight=lm_weight, ilm_weight=ilm_weight, length_bonus=length_bonus, return_lm=return_lm,
+                                      ctc_weight=ctc_weight, return_ctc=return_ctc)
 
     @torch.no_grad()
     def beam_search(self, enc_state, lengths, beam_width=5, block=64):

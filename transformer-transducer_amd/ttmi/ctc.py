@@ -10,7 +10,7 @@ import torch
 
 from . import ops
 
-__all__ = ["CTCLoss", "ctc_loss", "ctc_greedy_decode", "ctc_align", "CTCAlignment"]
+__all__ = ["CTCLoss", "ctc_loss", "ctc_greedy_decode", "ctc_align", "CTCAlignment", "ctc_score"]
 
 CTCAlignment = collections.namedtuple("CTCAlignment", "path spans score expected mass duration")
 
@@ -109,6 +109,41 @@ def ctc_greedy_decode(logits, act_lens=None, blank=0):
             raise RuntimeError("CTC greedy decode: the head produced no finite maximum at frame %d of utterance %d (NaN logits?)" % (-n - 1, b))
         out.append(host[b, 1:1 + n].tolist())
     return out
+
+
+@torch.no_grad()
+def ctc_score(logits, hypotheses, act_lens=None, blank=0):
+    """The CTC log-likelihood of every hypothesis on the logits of its utterance: logits f32 [B, T, V] on the GPU (un-normalised),
+    hypotheses = per utterance a list of token lists (an utterance may have none), act_lens integer [B] (None: every utterance has T
+    frames) -> f64 device tensor [P], the hypotheses in flattening order; -inf where no alignment is feasible (fewer frames than tokens
+    plus adjacent repeats).  The logits are shared by an utterance's hypotheses, not expanded (include/ttmi.h, ttmi_ctc_score_hyps);
+    the value is -ctc_loss(reduction='none') of the same tokens.  No host synchronisation."""
+    if not logits.is_cuda:
+        raise ValueError("ctc: logits must live on the GPU (the MI355X build has no CPU path)")
+    if logits.dim() != 3:
+        raise ValueError("ctc: logits must be [batch, T, vocab]")
+    B, T, _ = logits.shape
+    if len(hypotheses) != B:
+        raise ValueError("ctc_score: one list of hypotheses per utterance, got %d for a batch of %d" % (len(hypotheses), B))
+    if act_lens is None:
+        act_lens = torch.full((B,), T, dtype=torch.int32, device=logits.device)
+    _, act_lens, _ = _lengths(logits, None, act_lens, None)
+    flat = [(b, [int(v) for v in h]) for b in range(B) for h in hypotheses[b]]
+    if not flat:
+        return torch.empty(0, dtype=torch.float64, device=logits.device)
+    U = max(len(h) for _, h in flat)
+    if U > 1023:
+        raise ValueError("ctc_score: a hypothesis of %d tokens (at most 1023)" % U)
+    host = torch.zeros(len(flat), U + 2, dtype=torch.int64)             # utterance | length | tokens: one transfer
+    for p, (b, h) in enumerate(flat):
+        host[p, 0], host[p, 1] = b, len(h)
+        if h:
+            host[p, 2:2 + len(h)] = torch.tensor(h, dtype=torch.int64)
+    dev = host.to(logits.device)
+    x = logits.detach()
+    if x.dtype is not torch.float32 or ops.row_pitch(x) is None:
+        x = x.float().contiguous()
+    return ops.ctc_score_hyps(x, act_lens, dev[:, 2:], dev[:, 1].to(torch.int32), dev[:, 0].to(torch.int32), int(blank))
 
 
 @torch.no_grad()

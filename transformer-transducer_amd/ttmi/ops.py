@@ -455,6 +455,39 @@ def ctc_emit_stats(workspace, labels, act_lens, label_lens, B, T, V, blank=0):
     return expected, mass, duration
 
 
+def ctc_score_workspace(B, T, device):
+    """scratch of ctc_score_hyps (the log-sum-exp of every row): f32 words, never empty (the entry wants a pointer whatever the shape)"""
+    n = _sized("ttmi_ctc_score_ws_bytes", c_int(B), c_int(T))
+    return torch.empty(max((n + 3) // 4, 1), dtype=torch.float32, device=device)
+
+
+def ctc_score_hyps(logits, act_lens, hyp, hyp_len, utt=None, blank=0, workspace=None):
+    """logits f32 [B, T, V] (dense or row-padded view), act_lens int32 [B]; hyp int64 [P, U] (row pitch = stride(0): a column view of a
+    beam's histories goes in as it is), hyp_len int32 [P], utt int32 [P] or None (None: P = B * N, pair p belongs to utterance p // N) ->
+    score f64 [P]: the CTC log-likelihood of hypothesis p on the logits of its utterance, -inf where no alignment is feasible
+    (include/ttmi.h: ttmi_ctc_score_hyps).  Device only, no synchronisation."""
+    _need_cuda(logits, act_lens, hyp, hyp_len, utt, workspace)
+    if logits.dim() != 3 or logits.dtype is not torch.float32:
+        raise ValueError("ctc: logits must be f32 [B, T, V], got %s %s" % (logits.dtype, tuple(logits.shape)))
+    ld = row_pitch(logits)
+    if ld is None:
+        raise ValueError("ctc: logits must be dense or a [..., :V] view of a row-padded buffer")
+    B, T, V = logits.shape
+    if hyp.dim() != 2 or hyp.dtype is not torch.int64 or (hyp.numel() and hyp.stride(1) != 1) or (hyp.shape[0] > 1 and hyp.stride(0) < hyp.shape[1]):
+        raise ValueError("ctc_score_hyps: hyp must be int64 [P, U] with unit column stride")
+    P, U = hyp.shape
+    for name, t, n in (("act_lens", act_lens, B), ("hyp_len", hyp_len, P), ("utt", utt, P)):
+        if t is not None and (t.dim() != 1 or t.shape[0] != n or t.dtype is not torch.int32 or not t.is_contiguous()):
+            raise ValueError("ctc_score_hyps: %s must be contiguous int32 [%d]" % (name, n))
+    _trace("ctc_score_hyps", B, T, P, U)
+    ws = ctc_score_workspace(B, T, logits.device) if workspace is None else workspace
+    score = torch.empty(P, dtype=torch.float64, device=logits.device)
+    check(lib().ttmi_ctc_score_hyps(_p(logits), c_long(ld), _p(act_lens), c_int(B), c_int(T), c_int(V), c_int(blank), _p(hyp),
+                                    c_long(hyp.stride(0) if P > 1 else max(U, 1)), _p(hyp_len), _p(utt), c_int(P), c_int(U), _p(ws), _p(score),
+                                    _stream()), "ttmi_ctc_score_hyps")
+    return score
+
+
 def linear_nt(x, w, out, bias=None, prec=0, accumulate=False):
     """out[M, N] (f32, row pitch = out.stride(0)) (+)= x[M, K] @ w[N, K]^T (+ bias): the library's generic GEMM on f32 operands - exact-f32
     MFMA in the fp32 mode, the three-term bf16 split in the bf16x3 mode, bf16 MFMA with f32 accumulation and output in the bf16 mode"""
