@@ -323,6 +323,69 @@ int ttmi_mono_loss_bwd(const void* logits, int dtype, long ldv, const int* label
                        int B, int T, int U1, int V, int blank, const void* workspace, const float* grad_out,
                        int grad_out_stride, float scale, void* grad, long ldg, void* stream);
 
+/* ---- token-and-duration transducer (TDT; Xu et al., ICML 2023; no reference counterpart) ---------------------------------------------------
+ * The joint predicts a token AND the number of frames that decision consumes.  A row is z[b,t,u,0 : V+D] with pitch ldv >= V + D: V token
+ * columns followed by D duration columns, each sub-row normalised by itself.  V is the TOKEN count.  durations: a HOST array of D entries,
+ * copied into the launch: distinct integers in [1, 8], at most 8 of them, strictly increasing (no duration 0: every decoder here consumes
+ * the emitting frame).  With durations = (1) this is the monotonic lattice above.  Other arguments as for ttmi_mono_loss_fwd / _bwd: dtype
+ * 0 = f32, 1 = bf16; labels i32 [B,U1-1], clamped to [0, V-1]; act_lens, label_lens i32 [B], T_b clamped to [1, T], U_b to [0, U1-1]; blank
+ * in [0, V); U1 <= 1024.  With lt = log_softmax(z[0:V]), ld = log_softmax(z[V:V+D]), lpb(t,u) = lt[blank], lpl(t,u) = lt[y_{u+1}] for
+ * u < U_b, ld_j(t,u) = ld[j] the log-probability of durations[j] = d_j:
+ *     alpha(0,0) = 0, everything else -inf
+ *     alpha(t,u) = logsumexp over j with t - d_j >= 0 of   alpha(t-d_j, u)   + lpb(t-d_j, u)   + ld_j(t-d_j, u)
+ *                                                          alpha(t-d_j, u-1) + lpl(t-d_j, u-1) + ld_j(t-d_j, u-1)    (u >= 1)
+ *                                                                                              1 <= t <= T_b, 0 <= u <= U_b
+ *     ll = alpha(T_b, U_b),  costs[b] = -ll
+ *     beta(T_b,U_b) = 0;  beta(t,u) = logsumexp over j with t + d_j <= T_b of   lpb(t,u) + ld_j(t,u) + beta(t+d_j, u)
+ *                                                                               lpl(t,u) + ld_j(t,u) + beta(t+d_j, u+1)   (u < U_b)
+ * No terminal blank: a path is a sequence of decisions that lands EXACTLY on frame T_b.  A move that would overshoot (t + d_j > T_b) does
+ * not exist in the lattice; its probability mass is lost, as in the published loss.
+ * ttmi_tdt_loss_bwd, with g = scale * grad_out[b * grad_out_stride], for t < T_b, u <= U_b and each j with t + d_j <= T_b (0 otherwise):
+ *     e_b,j = exp(alpha(t,u) + lpb + ld_j + beta(t+d_j, u)   - ll)
+ *     e_l,j = exp(alpha(t,u) + lpl + ld_j + beta(t+d_j, u+1) - ll)         (0 for u = U_b)
+ *     E_b = sum_j e_b,j   E_l = sum_j e_l,j   E_j = e_b,j + e_l,j   occ = E_b + E_l = exp(alpha(t,u) + beta(t,u) - ll)
+ *     d z[k]     = g * ( softmax_tok[k] * occ - [k == blank] E_b - [k == y_{u+1}] E_l )        0 <= k < V
+ *     d z[V + j] = g * ( softmax_dur[j] * occ - E_j )                                          0 <= j < D
+ * Both sub-rows sum to zero.  A label equal to `blank` is not rejected.  Rows outside [0,T_b) x [0,U_b] are exact zeros, columns
+ * [V+D, ldg) are zeros; grad (the logits' dtype, pitch ldg >= V + D) may alias logits when ldg == ldv.  An utterance with no path - U_b > T_b,
+ * or T_b not a sum of durations (durations = (2) with an odd T_b) - has costs[b] = +inf and all-zero gradient rows, never NaN; its
+ * neighbours are unaffected.  Alpha and beta are carried in fp64 in a fixed summation order (alpha: by source frame; beta: j ascending).
+ * workspace: ttmi_tdt_workspace_bytes(B, T, U1, D) bytes, 8-byte aligned; the forward fills it, the backward reads it.  No allocation, host
+ * synchronisation, memset node or floating-point atomic: both calls may be captured in a HIP graph, and two runs give the same bits.
+ * rc < 0 with a ttmi_last_error text, before any launch, on a null pointer, a shape outside the limits, D outside [1,8], a duration outside
+ * [1,8] or durations not strictly increasing, ldv (or ldg) < V + D.
+ * NOT built on this lattice: the exp-domain form, FastEmit, alignment / emission statistics, distillation, beam search.
+ *
+ * Greedy decoding, the lockstep-over-symbol-steps pair of ttmi_greedy_scan_batch_lp / ttmi_greedy_advance_lp with jumps.  Per utterance, at
+ * frame t against the current label state: k* = argmax z[0:V], j* = argmax z[V:V+D] (in both the LOWEST index wins a tie and a NaN counts as
+ * the largest value: the order of ttmi_greedy_scan_batch), d = durations[j*], the decision's log-probability is lt[k*] + ld[j*].  Blank:
+ * t += d.  Token: k* is emitted on frame t, then t += d and the label state advances.  The utterance ends when t >= T_len[b] (the decoder
+ * may overshoot: it then ends).
+ * ttmi_tdt_scan_batch: logits [B, n, V+D] (row pitch ld >= V + D) = the joint of frames t[b] .. t[b] + n - 1 of every utterance against its
+ * own label state.  For every row that exists (need[b] != 0, t[b] + r < T_len[b]): dec[b][r] = (k*, j*) (device i32 [B, n, 2]),
+ * lp[b][r] = (lt[k*], ld[j*]) (device f32 [B, n, 2]), one pass per sub-row in f32 (bf16 widened exactly); NaN where the sub-row's
+ * log-sum-exp is not finite.  Other rows are NOT written.
+ * ttmi_tdt_advance: one thread per utterance with need[b] follows the jumps through the block from row 0, t0 = t[b]: the decision of row r
+ * adds lp[b][r][0] + lp[b][r][1] to score[b] (device f64 [B], zeroed by the caller before the first block; one thread, row order: the same
+ * bits in every run) and moves r on by d.  It stops at the first token - hist[b][n_hist] = k*, frames[b][c] = t0 + r, tok_lp[b][c] =
+ * lt[k*], tok_dur[b][c] = d at c = count[b] (i32 / f32 / i32 [B, ld_det], count[b] < ld_det required), count[b] += 1, need[b] = 0 - or when
+ * the jump leaves the block or the utterance.  A jump that leaves the block CARRIES OVER: t[b] becomes t0 + r exactly, not t0 + n.  Once
+ * t[b] >= T_len[b]: need[b] = 0, done[b] = 1 (also straight after a token).  Utterances with need[b] == 0 are left alone.  flags[0] =
+ * utterances that still need a symbol in this step, flags[1] = utterances not finished, as ttmi_greedy_advance leaves them (written, not
+ * added: nothing is zeroed first).  `durations` is a HOST array as above.  Neither call allocates, synchronises with the host or issues a
+ * memset node; both may be captured in a HIP graph. */
+size_t ttmi_tdt_workspace_bytes(int B, int T, int U1, int D);
+int ttmi_tdt_loss_fwd(const void* logits, int dtype, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                      int B, int T, int U1, int V, int blank, const int* durations, int D, void* workspace, float* costs, void* stream);
+int ttmi_tdt_loss_bwd(const void* logits, int dtype, long ldv, const int* labels, const int* act_lens, const int* label_lens,
+                      int B, int T, int U1, int V, int blank, const int* durations, int D, const void* workspace, const float* grad_out,
+                      int grad_out_stride, float scale, void* grad, long ldg, void* stream);
+int ttmi_tdt_scan_batch(const void* logits, int dtype, long ld, int B, int n, int V, int D, const int* t, const int* T_len,
+                        const int* need, int* dec, float* lp, void* stream);
+int ttmi_tdt_advance(const int* dec, const float* lp, int B, int n, int blank, const int* durations, int D, int n_hist, long* hist,
+                     long ld_hist, int* t, const int* T_len, int* need, int* done, int* count, int* flags, int* frames, float* tok_lp,
+                     int* tok_dur, long ld_det, double* score, void* stream);
+
 /* ---- forced alignment and emission-time statistics on the monotonic lattice (no reference counterpart) ---------------------------------
  * The twins of ttmi_rnnt_align / _emit_stats on the lattice above.  Both READ the workspace a finished ttmi_mono_loss_fwd left on the same
  * (B, T, U1) - lpb, lpl, alpha, beta, ll - and write nothing into it: a ttmi_mono_loss_bwd issued after them gives the same bits as one

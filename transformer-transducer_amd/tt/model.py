@@ -152,9 +152,16 @@ class _JointLossFn(torch.autograd.Function):
         `weights`).  A chunk then runs joint_fwd, the topology's loss forward, kd_loss_fwd, the topology's loss gradient OUT of place (FastEmit
         included; in the bf16x3 mode the f32 gradient goes through joint_bwd's own split pass, as on the monotonic lattice), kd_loss_bwd
         adding scale * distill_weight * d KD onto that gradient, joint_bwd.  A second chunk buffer is alive meanwhile; the 2 GB budget of
-        default_loss_chunk leaves room for it, so the chunk size is the same.  No exp-domain form"""
+        default_loss_chunk leaves room for it, so the chunk size is the same.  No exp-domain form.  `topology` may also be a lattice RECORD
+        instead of one of the two names: an ops.TDTLattice (token-and-duration transducer: wp has V + D rows, the loss entries are
+        ttmi_tdt_loss_fwd / _bwd) runs the plain chunk form as 'monotonic' does; FastEmit and distillation are not built on it"""
         fe = ops.check_fastemit(fastemit_lambda)
-        lat = ops.lattice(topology, fe)
+        if isinstance(topology, str):
+            lat = ops.lattice(topology, fe)
+        else:
+            lat = topology
+            if fe > 0.0 or (distill is not None and float(distill_weight) != 0.0):
+                raise ValueError("%s: FastEmit and distillation are not built on this lattice" % lat.name.upper())
         if not lat.has_exp_forms and exp_state is not None:
             raise ValueError("topology='%s' has no exp-domain form" % lat.name)
         kd = distill is not None and float(distill_weight) != 0.0
@@ -452,6 +459,9 @@ class DeferredLogits(torch.Tensor):
     def rnnt_loss(self, labels, act_lens, label_lens, blank=0, reduction="mean", *, fastemit_lambda=0.0, topology="rnnt"):
         """the loss of train.py:53 on this handle's logits without forming them (called by warprnnt_pytorch.rnnt_loss; arguments already
         certified there).  None when this case has to go through the real logits (per-utterance costs that need gradients)."""
+        if getattr(self._joint, "tdt_durations", None) is not None:
+            raise ValueError("TDT: RNNTLoss on the logits of a token-and-duration model is not built (its rows are V + D wide): use "
+                             "ttmi.tdt.TDTLoss or Transducer.loss")
         if self._real is not None:
             return None
         grad = self._grad_mode and torch.is_grad_enabled()
@@ -477,6 +487,8 @@ class DeferredLogits(torch.Tensor):
         certified there): the chunked forward-only loop of Transducer.align.  None when the handle was already used as a tensor (the
         caller then aligns the real logits).  topology='monotonic': the same loop on the one-decision-per-frame lattice, in the plain
         chunk form at the memory form's chunk size (no exp-domain branch)."""
+        if getattr(self._joint, "tdt_durations", None) is not None:
+            raise ValueError("TDT: forced alignment is not built for a token-and-duration model")
         if self._real is not None:
             return None
         j = self._joint
@@ -666,8 +678,13 @@ class Transducer(nn.Module):
         self.config = config
         self.encoder = BuildEncoder(config)
         self.decoder = BuildDecoder(config)
+        # token-and-duration transducer (ttmi.tdt; config.tdt_durations absent, None or empty: today's module, state_dict and bits): the joint's
+        # projection gets D more rows, the duration logits, behind the vocab_size token rows
+        self.tdt_durations = ops.check_durations(config.tdt_durations) if config.tdt_durations else None
         self.joint = JointNet(input_size=config.joint.input_size, inner_dim=config.joint.inner_size,
-                              vocab_size=config.vocab_size)
+                              vocab_size=config.vocab_size + len(self.tdt_durations or ()))
+        if self.tdt_durations is not None:
+            self.joint.tdt_durations = self.tdt_durations      # (a DeferredLogits handle knows its joint only: RNNTLoss on it is refused)
         if config.share_embedding:
             # the reference's branch dereferences self.decoder.embedding, which does not exist (tt/model.py:53-56)
             raise AttributeError("'BuildDecoder' object has no attribute 'embedding' (share_embedding is broken upstream)")
@@ -731,7 +748,20 @@ class Transducer(nn.Module):
         shape, dtype or device."""
         from warprnnt_pytorch import check_lengths as certify, check_monotonic_lengths as monotonic_lengths
         fastemit_lambda = ops.check_fastemit(fastemit_lambda)
-        lat = ops.lattice(topology, fastemit_lambda)
+        if self.tdt_durations is not None:
+            # token-and-duration model: the plain chunk form on its own lattice (joint_fwd, tdt_loss_fwd, tdt_loss_bwd in place, joint_bwd);
+            # ctc_weight and utterance_weights live outside the lattice and work as always
+            if topology != "rnnt":
+                raise self._tdt_not_built("loss(topology=%r)" % (topology,))
+            if exp_domain:
+                raise self._tdt_not_built("the exp-domain loss form")
+            if fastemit_lambda > 0.0:
+                raise self._tdt_not_built("FastEmit")
+            if distill is not None and self._distill_weight(distill_weight) != 0.0:
+                raise self._tdt_not_built("distillation")
+            lat = topology = ops.TDTLattice(self.tdt_durations)
+        else:
+            lat = ops.lattice(topology, fastemit_lambda)
         if exp_domain and not lat.has_exp_forms:
             raise ValueError("topology='%s' has no exp-domain form: leave exp_domain off" % lat.name)
         distill_weight = self._distill_weight(distill_weight)
@@ -747,7 +777,12 @@ class Transducer(nn.Module):
         labels, al, ll = (t.to(device=enc_state.device, dtype=torch.int32).contiguous() for t in (targets, inputs_length, targets_length))
         certify(labels, al, ll, B, T, U1, check_lengths)
         if lat.label_takes_frame and check_lengths:
-            monotonic_lengths(al, ll)                # ValueError for an utterance with more labels than frames
+            try:
+                monotonic_lengths(al, ll)            # ValueError for an utterance with more labels than frames
+            except ValueError:
+                if self.tdt_durations is None:
+                    raise
+                raise ValueError("TDT: an utterance has more labels than frames (label_lengths > lengths)") from None
         ops.weights_fresh()
         prec = default_precision()
         if chunk is None:
@@ -763,6 +798,16 @@ class Transducer(nn.Module):
         if ctc_weight > 0.0:
             return rnnt + ctc_weight * self._ctc_from_states(enc_state, labels, al, ll, reduction)
         return rnnt
+
+    @staticmethod
+    def _tdt_not_built(what):
+        """the error of every entry point that is not built for a token-and-duration model (config.tdt_durations)"""
+        from ttmi.tdt import not_built
+        return not_built(what)
+
+    def _refuse_tdt(self, what):
+        if self.tdt_durations is not None:
+            raise self._tdt_not_built(what)
 
     @staticmethod
     def _distill_weight(w):
@@ -781,6 +826,7 @@ class Transducer(nn.Module):
         outside the ragged lattice.  Under no_grad, without materialising the logits: per chunk of `loss()`'s plain form joint_fwd then
         kd_collapse, and the chunk's logits are dropped before the next chunk.  12 bytes per node (9.8 MB for a whole C2 batch): it can be
         computed once per utterance and cached.  The encoders run in whatever mode the module is in: call it in eval() mode."""
+        self._refuse_tdt("lattice_posteriors / distillation")
         from warprnnt_pytorch import check_lengths as certify
         labels, al, ll = (t.to(dtype=torch.int32) for t in (targets, inputs_length, targets_length))
         certify(labels.contiguous(), al.contiguous(), ll.contiguous(), inputs.shape[0], 0, targets.shape[1] + 1, False)
@@ -867,6 +913,7 @@ class Transducer(nn.Module):
         details=True: -> (loss, MWERDetails(hypotheses, errors i32 [rows], posteriors f64 [rows], costs f32 [rows], expected_errors f64 [B]));
         the per-row fields cover the whole row table: transcript rows carry errors 0 and posterior 0."""
         from ttmi import metrics
+        self._refuse_tdt("MWER training (mwer_loss)")
         fastemit_lambda = ops.check_fastemit(fastemit_lambda)
         ops.check_topology(topology, fastemit_lambda)
         rnnt_weight = float(rnnt_weight)
@@ -1063,6 +1110,7 @@ class Transducer(nn.Module):
     def _align(self, method, topology, inputs, inputs_length, targets, targets_length, chunk, check_lengths, exp_domain, stats):
         """the body of align / align_monotonic (`method`: the caller's name, for its error message)"""
         from warprnnt_pytorch import check_lengths as certify, check_monotonic_lengths as monotonic_lengths
+        self._refuse_tdt("forced alignment / emission statistics (%s)" % method)
         lat = ops.lattice(topology)
         labels, al, ll = (t.to(dtype=torch.int32) for t in (targets, inputs_length, targets_length))
         certify(labels.contiguous(), al.contiguous(), ll.contiguous(), inputs.shape[0], 0, targets.shape[1] + 1, False)
@@ -1162,7 +1210,10 @@ class Transducer(nn.Module):
         label state and the first non-blank frame is found on the device (ttmi_greedy_scan): one host sync per emitted
         symbol instead of one per frame.  The label-encoder re-runs replay captured graphs (one per history length, see
         _LabelStateGraphs).  details=True: -> DecodeResult (tokens, emission frames, token log-probabilities, path score), from
-        `decode_batch`'s device-side bookkeeping on a batch of one."""
+        `decode_batch`'s device-side bookkeeping on a batch of one.  A token-and-duration model goes through `decode_batch` on a batch of
+        one whatever `details` says (its jumps live in the TDT kernel pair)."""
+        if self.tdt_durations is not None:
+            return self.decode_batch(enc_state[None], [int(lengths)], block=block, details=details)[0]
         if details:
             return self.decode_batch(enc_state[None], [int(lengths)], block=block, details=True)[0]
         token_list = [0]
@@ -1225,7 +1276,13 @@ class Transducer(nn.Module):
         one pass over each row of logits also yields log P(blank) and log P(argmax), the advance books the emission frame and log-probability
         of every token and the f64 log-probability of the greedy path (DecodeResult for what that score is and is not).  Same joint and
         label-encoder calls, same host reads; the details follow the rows through the shrinking batch like the histories and come back in
-        the one transfer at the end."""
+        the one transfer at the end.
+
+        A token-and-duration model (config.tdt_durations) runs the same lockstep with ttmi_tdt_scan_batch / ttmi_tdt_advance: every decision
+        jumps by the duration it predicts, a jump that leaves the block carries over into the next one, and details=True gives
+        ttmi.tdt.TDTDecodeResult (the DecodeResult fields and the tokens' durations)."""
+        if self.tdt_durations is not None:
+            return self._decode_batch_tdt(enc_states, lengths, block, details)
         if details and not enc_states.is_cuda:
             raise ValueError("decode_batch(details=True): enc_states must live on the GPU (the MI355X build has no CPU path)")
         dev = enc_states.device
@@ -1322,11 +1379,99 @@ class Transducer(nn.Module):
         counts = final_count.cpu().tolist()
         return [final[b, 1:1 + counts[b]].tolist() for b in range(B)]
 
+    def _decode_batch_tdt(self, enc_states, lengths, block, details):
+        """decode_batch for a token-and-duration model: the same symbol-step lockstep, shrinking batch and label-encoder graphs, with the TDT
+        pair in place of the greedy pair.  There is one pair only, and it always books the details (frames, log-probabilities, durations,
+        score); details=False returns the token lists alone.  block (default 64): the frames scored per joint call.  A jump skips rows
+        the block has scored, so a TDT block of n frames holds n / (mean duration) decisions; 64 keeps the SPAN of a block, and with it the
+        joint calls and host reads per symbol step, at what the frame-by-frame decoder has."""
+        from ttmi.tdt import TDTDecodeResult
+        if not enc_states.is_cuda:
+            raise ValueError("decode_batch: a token-and-duration model decodes on the GPU only (the MI355X build has no CPU path)")
+        durs = self.tdt_durations
+        dev = enc_states.device
+        B, T = enc_states.shape[0], enc_states.shape[1]
+        n_frames = 64 if block is None else int(block)
+        T_len = torch.as_tensor(lengths, dtype=torch.int32).to(dev).clamp(max=T).contiguous()
+        graphs = self._label_state_graphs(dev, B) if self.config.decode_batch_graphs is not False else None
+        final_hist = torch.zeros(B, T + 2, dtype=torch.long, device=dev)   # column 0 = the start symbol (blank); at most one symbol per frame
+        final_count = torch.zeros(B, dtype=torch.int32, device=dev)
+        final_frames = torch.zeros(B, T + 1, dtype=torch.int32, device=dev)
+        final_lp = torch.zeros(B, T + 1, dtype=torch.float32, device=dev)
+        final_dur = torch.zeros(B, T + 1, dtype=torch.int32, device=dev)
+        final_score = torch.zeros(B, dtype=torch.float64, device=dev)
+        hist, frames, tok_lp, tok_dur, score = (v.clone() for v in (final_hist, final_frames, final_lp, final_dur, final_score))
+        orig = torch.arange(B, device=dev)                           # the utterance each row of the (shrinking) batch belongs to
+        t = torch.zeros(B, dtype=torch.int32, device=dev)
+        need = torch.ones(B, dtype=torch.int32, device=dev)
+        done = torch.zeros(B, dtype=torch.int32, device=dev)
+        count = torch.zeros(B, dtype=torch.int32, device=dev)
+        flags = torch.zeros(2, dtype=torch.int32, device=dev)
+        rows = torch.arange(n_frames, device=dev, dtype=torch.long)[None, :]
+        dec = torch.zeros(B, n_frames, 2, dtype=torch.int32, device=dev)
+        lp = torch.zeros(B, n_frames, 2, dtype=torch.float32, device=dev)
+
+        def label_states(n_hist):
+            """label-encoder outputs at the last position of every history (all of length n_hist) -> [rows of the batch, 1, d]"""
+            if graphs is not None and n_hist <= graphs.MAX_L and hist.shape[0] == graphs.batch:
+                graphs.master[:, :n_hist].copy_(hist[:, :n_hist])
+                return graphs.state(n_hist)
+            return self.decoder(hist[:, :n_hist].contiguous())[:, -1:, :]
+
+        def keep_results():
+            for dst, src in ((final_hist, hist), (final_count, count), (final_frames, frames), (final_lp, tok_lp), (final_dur, tok_dur),
+                             (final_score, score)):
+                dst.index_copy_(0, orig, src)
+
+        n_hist = 1
+        dec_state = label_states(n_hist)
+        while True:
+            torch.sub(1, done, out=need)
+            while True:
+                idx = (t.long()[:, None] + rows).clamp_(max=T - 1)                             # frames t_b .. t_b + n_frames - 1 (beyond T_b: ignored by the scan)
+                logits = self.joint(enc_states[orig[:, None], idx], dec_state)                    # [rows, n_frames, 1, V + D]
+                ops.tdt_scan_batch(logits[:, :, 0, :], len(durs), t, T_len, need, dec, lp)
+                ops.tdt_advance(dec, lp, durs, n_hist, hist, t, T_len, need, done, count, flags, frames, tok_lp, tok_dur, score)
+                pending, alive = flags.tolist()                                                   # the batch's one host round trip per block
+                if pending == 0:
+                    break
+            if alive == 0:
+                break
+            if alive < hist.shape[0] and self.config.decode_batch_shrink is not False:
+                keep_results()
+                keep = torch.argsort(done, stable=True)[:alive]
+                hist, frames, tok_lp, tok_dur, score = hist[keep], frames[keep], tok_lp[keep], tok_dur[keep], score[keep]
+                orig, t, T_len, count = orig[keep], t[keep].contiguous(), T_len[keep].contiguous(), count[keep].contiguous()
+                dec, lp = dec[:alive], lp[:alive]
+                need = torch.zeros(alive, dtype=torch.int32, device=dev)
+                done = torch.zeros(alive, dtype=torch.int32, device=dev)
+            n_hist += 1
+            dec_state = label_states(n_hist)
+        keep_results()
+        if not details:
+            final = final_hist.cpu()
+            counts = final_count.cpu().tolist()
+            return [final[b, 1:1 + counts[b]].tolist() for b in range(B)]
+        # ONE transfer, as f64 (exact for token ids, counts, frames, durations and f32 log-probabilities)
+        packed = torch.cat([final_count.double()[:, None], final_score[:, None], final_hist[:, 1:T + 2].double(), final_frames.double(),
+                            final_lp.double(), final_dur.double()], dim=1).cpu()
+        out = []
+        for b in range(B):
+            c = int(packed[b, 0])
+            tok, frm, lpr, dur = (packed[b, 2 + i * (T + 1):2 + i * (T + 1) + c].tolist() for i in range(4))
+            out.append(TDTDecodeResult([int(v) for v in tok], [int(v) for v in frm], lpr, [int(v) for v in dur], float(packed[b, 1])))
+        return out
+
     @torch.no_grad()
     def recognize(self, inputs, inputs_length=None, audio_mask=None, details=False):
         """greedy recognition of a batch -> one token list per utterance; details=True -> one DecodeResult per utterance (tokens, emission
         frames, token log-probabilities, path score), every utterance through decode_batch's device-side bookkeeping (a batch of one too;
-        with config.batched_decode = False one decode(details=True) per utterance)"""
+        with config.batched_decode = False one decode(details=True) per utterance).  A token-and-duration model (config.tdt_durations)
+        always decodes through decode_batch's TDT pair, a batch of one included; details=True -> ttmi.tdt.TDTDecodeResult"""
+        if self.tdt_durations is not None:
+            if not inputs.is_cuda:
+                raise ValueError("recognize: a token-and-duration model decodes on the GPU only (the MI355X build has no CPU path)")
+            return self.decode_batch(self.encoder(inputs, audio_mask), inputs_length, details=details)
         if details:
             if not inputs.is_cuda:
                 raise ValueError("recognize(details=True): inputs must live on the GPU (the MI355X build has no CPU path)")
@@ -1379,6 +1524,7 @@ class Transducer(nn.Module):
         of this runs.  ValueError on a module without the head, or when max(lengths) > 1023 (the scorer's longest hypothesis).
         The same search over frames that arrive in blocks: `beam_search_state` (ttmi.beam.BeamSearch; this loop stays beside it as it is).
         Not built: a cache of label states for sequences seen on earlier frames, a captured graph of the loop."""
+        self._refuse_tdt("beam search (beam_decode_batch / recognize_nbest, ctc_weight= rescoring included)")
         if not enc_states.is_cuda:
             raise ValueError("beam_decode_batch: enc_states must live on the GPU (the MI355X build has no CPU path)")
         W = int(beam_width)
@@ -1563,6 +1709,7 @@ class Transducer(nn.Module):
         frames, bit for bit, however they were split.  context / lm / lm_weight / ilm_weight / length_bonus as there.  history = "full": the
         label state of a hypothesis is decoder([start] + tokens) as there; "stream": the streaming recogniser's rule, decoder(the last
         max_history tokens) without a leading start symbol.  capacity = the columns the history buffers start with (default 64; they grow)."""
+        self._refuse_tdt("resumable beam search (beam_search_state, StreamingRecognizer)")
         from ttmi.beam import BeamSearch
         return BeamSearch(self, B, beam_width, context=context, lm=lm, lm_weight=lm_weight, ilm_weight=ilm_weight, length_bonus=length_bonus,
                           history=history, max_history=max_history, capacity=capacity)
@@ -1574,6 +1721,7 @@ class Transducer(nn.Module):
         beam_width) DecodeResult, best first, with merged, comparable scores; `context` / `return_bias`: contextual biasing, `lm` /
         `lm_weight` / `ilm_weight` / `length_bonus` / `return_lm`: language-model fusion, `ctc_weight` / `return_ctc`: rescoring of the
         final beam with the CTC head, see there"""
+        self._refuse_tdt("beam search (recognize_nbest)")
         if not inputs.is_cuda:
             raise ValueError("recognize_nbest: inputs must live on the GPU (the MI355X build has no CPU path)")
         enc_states = self.encoder(inputs, audio_mask)
@@ -1595,6 +1743,7 @@ class Transducer(nn.Module):
           * on the expanding frame one joint call scores all hypotheses, softmax + top-(beam_width + 1) run on the device, and ONE host read
             brings the beam_width x (beam_width + 1) (probability, symbol) pairs back for the reference's own bookkeeping.
         Host reads: two per expansion + one per scanned block, instead of (1 + beam_width) per frame."""
+        self._refuse_tdt("beam search (beam_search)")
         if not enc_state.is_cuda or not block:
             return self._beam_search_per_frame(enc_state, lengths, beam_width)
         dev, W, T = enc_state.device, beam_width, int(lengths)
@@ -1657,6 +1806,7 @@ class Transducer(nn.Module):
         """(round 2; `beam_search(block=0)`) Restatement of the reference's beam search (tt/model.py:110-179) including its quirks: frames advance on the
         currently most probable hypothesis; expansion happens only when that hypothesis predicts a non-blank; child
         token lists persist across expansions (they are appended to, never re-seeded from their parents)."""
+        self._refuse_tdt("beam search (beam_search)")
         dev = enc_state.device
 
         def posterior(tokens, t):
@@ -1701,5 +1851,6 @@ class Transducer(nn.Module):
 
     @torch.no_grad()
     def recognize_beam_search(self, inputs, inputs_length, audio_mask=None):
+        self._refuse_tdt("beam search (recognize_beam_search)")
         enc_states = self.encoder(inputs, audio_mask)
         return [self.beam_search(enc_states[b], inputs_length[b], beam_width=5) for b in range(inputs.size(0))]

@@ -32,6 +32,9 @@ from . import ops
 class BeamSearch:
     def __init__(self, model, B, beam_width=4, context=None, lm=None, lm_weight=0.0, ilm_weight=0.0, length_bonus=0.0, history="full",
                  max_history=40, capacity=None):
+        if getattr(model, "tdt_durations", None) is not None:
+            from .tdt import not_built
+            raise not_built("resumable beam search (BeamSearch)")
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise ValueError("beam_search_state: the model must live on the GPU (the MI355X build has no CPU path)")

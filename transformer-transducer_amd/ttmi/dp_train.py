@@ -97,6 +97,26 @@ class _Quiet:
         return lambda *a, **k: None
 
 
+def make_criterion(config):
+    """the transducer criterion of a run, from two optional keys of config.training and one of config.model: tdt_durations makes the model a
+    token-and-duration transducer, whose criterion is ttmi.tdt.TDTLoss; loss_topology other than 'rnnt' or fastemit_lambda > 0 together with
+    it is a ValueError (neither is built for TDT)"""
+    from warprnnt_pytorch import RNNTLoss
+    criterion = RNNTLoss(fastemit_lambda=config.training.get('fastemit_lambda', 0.0))     # FastEmit: an optional key of this driver
+    topology = config.training.get('loss_topology', 'rnnt')     # the loss lattice, another optional key: 'monotonic' = the decoders' one-decision-per-frame lattice
+    durations = config.model.get('tdt_durations')
+    if durations:
+        from ttmi.tdt import TDTLoss, not_built
+        if topology != 'rnnt':
+            raise not_built("training.loss_topology = %r" % (topology,))
+        if criterion.fastemit_lambda > 0.0:
+            raise not_built("FastEmit (training.fastemit_lambda > 0)")
+        return TDTLoss(durations)
+    if topology != 'rnnt':
+        criterion = RNNTLoss(fastemit_lambda=criterion.fastemit_lambda, topology=topology)
+    return criterion
+
+
 def main(argv=None):
     import yaml
     parser = argparse.ArgumentParser()
@@ -163,10 +183,7 @@ def main(argv=None):
         se = torch.tensor([start_epoch], device=dev)
         dist.broadcast(se, 0)
         start_epoch = int(se)
-    criterion = RNNTLoss(fastemit_lambda=config.training.get('fastemit_lambda', 0.0))     # FastEmit: an optional key of this driver
-    topology = config.training.get('loss_topology', 'rnnt')     # the loss lattice, another optional key: 'monotonic' = the decoders' one-decision-per-frame lattice
-    if topology != 'rnnt':
-        criterion = RNNTLoss(fastemit_lambda=criterion.fastemit_lambda, topology=topology)
+    criterion = make_criterion(config)
     if ctc_weight > 0.0:
         criterion = CTCAugmentedCriterion(criterion, model, ctc_weight)
     for epoch in range(start_epoch, config.training.epochs):

@@ -279,6 +279,140 @@ def mono_emit_stats(workspace, act_lens, label_lens, B, T, U1):
     return _MONO._emit_stats(workspace, act_lens, label_lens, B, T, U1)
 
 
+# ----------------------------------------------------------------------------- token-and-duration transducer (csrc/tdt.hip)
+TDT_MAX_DURATION = 8
+
+
+def check_durations(durations):
+    """-> durations as a tuple of ints; ValueError unless they are distinct integers in [1, 8], at most 8 of them, in strictly increasing
+    order.  Duration 0 (several tokens on one frame) is refused: every decoder of this library consumes the emitting frame."""
+    try:
+        ds = tuple(durations)
+    except TypeError:
+        raise ValueError("TDT durations must be a sequence of integers in [1, %d], got %r" % (TDT_MAX_DURATION, durations)) from None
+    if not 1 <= len(ds) <= TDT_MAX_DURATION:
+        raise ValueError("TDT durations: between 1 and %d durations, got %d" % (TDT_MAX_DURATION, len(ds)))
+    for d in ds:
+        if isinstance(d, bool) or not isinstance(d, int):
+            raise ValueError("TDT durations must be integers, got %r" % (d,))
+        if d == 0:
+            raise ValueError("TDT duration 0 (several tokens on one frame) is not built: every decoder here consumes the emitting frame; "
+                             "durations must lie in [1, %d]" % TDT_MAX_DURATION)
+        if not 1 <= d <= TDT_MAX_DURATION:
+            raise ValueError("TDT duration %d outside [1, %d]" % (d, TDT_MAX_DURATION))
+    if any(b <= a for a, b in zip(ds, ds[1:])):
+        raise ValueError("TDT durations must be strictly increasing, got %r" % (ds,))
+    return ds
+
+
+def _c_durations(durations):
+    ds = check_durations(durations)
+    return (c_int * len(ds))(*ds), c_int(len(ds))
+
+
+def _tdt_args(logits, D):
+    if logits.dim() != 4 or logits.dtype not in _DT or _DT[logits.dtype] > 1:
+        raise ValueError("TDT: logits must be an f32 / bf16 tensor [B, T, U1, V + D]")
+    B, T, U1, W = logits.shape
+    if W - D < 1:
+        raise ValueError("TDT: the last dimension (%d) must hold at least one token column and the %d duration columns" % (W, D))
+    ld = row_pitch(logits)
+    if ld is None:
+        raise ValueError("TDT: logits must be dense or a row-padded [..., :V + D] view")
+    return B, T, U1, W - D, ld
+
+
+def tdt_workspace(B, T, U1, D, device):
+    n = _sized("ttmi_tdt_workspace_bytes", c_int(B), c_int(T), c_int(U1), c_int(D))
+    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device)
+
+
+def tdt_loss_fwd(logits, labels, act_lens, label_lens, blank, durations, workspace):
+    """logits: f32 / bf16 [B, T, U1, V + D], dense or row-padded view: V token columns, then the D = len(durations) duration columns -> costs
+    f32 [B] on the token-and-duration lattice (include/ttmi.h: ttmi_tdt_loss_fwd); +inf for an utterance without a path"""
+    _need_cuda(logits, labels, act_lens, label_lens, workspace)
+    dur, D = _c_durations(durations)
+    B, T, U1, V, ld = _tdt_args(logits, D.value)
+    _trace("tdt_loss_fwd", B, T, U1, V, D.value)
+    costs = torch.empty(B, dtype=torch.float32, device=logits.device)
+    check(lib().ttmi_tdt_loss_fwd(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T),
+                                  c_int(U1), c_int(V), c_int(blank), dur, D, _p(workspace), _p(costs), _stream()), "ttmi_tdt_loss_fwd")
+    return costs
+
+
+def tdt_loss_bwd(logits, labels, act_lens, label_lens, blank, durations, workspace, grad_out, grad_out_stride, scale, inplace=False):
+    """scale * grad_out[b * grad_out_stride] * d costs[b] / d logits over all V + D columns, with the logits' pitch (pad columns zero);
+    inplace: written over the logits (ttmi_tdt_loss_bwd)"""
+    _need_cuda(logits, labels, act_lens, label_lens, workspace, grad_out)
+    dur, D = _c_durations(durations)
+    B, T, U1, V, ld = _tdt_args(logits, D.value)
+    _trace("tdt_loss_bwd", B, T, U1, V, D.value)
+    grad, ld = grad_buffer(logits, inplace)
+    check(lib().ttmi_tdt_loss_bwd(_p(logits), c_int(_DT[logits.dtype]), c_long(ld), _p(labels), _p(act_lens), _p(label_lens), c_int(B), c_int(T),
+                                  c_int(U1), c_int(V), c_int(blank), dur, D, _p(workspace), _p(grad_out), c_int(grad_out_stride),
+                                  c_float(scale), _p(grad), c_long(ld), _stream()), "ttmi_tdt_loss_bwd")
+    return grad
+
+
+def tdt_scan_batch(logits, D, t, T_len, need, dec, lp):
+    """logits [B, n, V + D] (f32 / bf16, row pitch = stride(-2)): for every existing row of the block, dec [B, n, 2] (i32) = (argmax token,
+    argmax duration index) and lp [B, n, 2] (f32) = their log-probabilities, each sub-row normalised by itself (include/ttmi.h:
+    ttmi_tdt_scan_batch); rows it skips keep what dec / lp held; device only, no synchronisation"""
+    B, n, W = logits.shape
+    _need_cuda(logits, t, T_len, need, dec, lp)
+    assert dec.dtype is torch.int32 and dec.is_contiguous() and tuple(dec.shape) == (B, n, 2)
+    assert lp.dtype is torch.float32 and lp.is_contiguous() and tuple(lp.shape) == (B, n, 2)
+    check(lib().ttmi_tdt_scan_batch(_p(logits), c_int(_DT[logits.dtype]), c_long(logits.stride(-2)), c_int(B), c_int(n), c_int(W - D), c_int(D),
+                                    _p(t), _p(T_len), _p(need), _p(dec), _p(lp), _stream()), "ttmi_tdt_scan_batch")
+
+
+def tdt_advance(dec, lp, durations, n_hist, hist, t, T_len, need, done, count, flags, frames, tok_lp, tok_dur, score, blank=0):
+    """follow the jumps through the scanned block (ttmi_tdt_advance): histories, frame positions (a jump that leaves the block carries over)
+    and the need / done flags move on the device; frames (i32) / tok_lp (f32) / tok_dur (i32) [B, ld_det] get the emission frame,
+    log-probability and duration of the symbol appended at column count[b]; score (f64 [B]) the log-probability of the decisions taken;
+    flags[0] = utterances that still need a symbol in this step, flags[1] = utterances not finished"""
+    B, n = dec.shape[0], dec.shape[1]
+    _need_cuda(dec, lp, hist, t, T_len, need, done, count, flags, frames, tok_lp, tok_dur, score)
+    dur, D = _c_durations(durations)
+    assert hist.dtype is torch.long and hist.stride(1) == 1
+    assert dec.dtype is torch.int32 and dec.is_contiguous() and lp.dtype is torch.float32 and lp.is_contiguous() and tuple(lp.shape) == (B, n, 2)
+    assert frames.dtype is torch.int32 and tok_lp.dtype is torch.float32 and tok_dur.dtype is torch.int32
+    assert frames.stride(1) == 1 and tok_lp.stride(1) == 1 and tok_dur.stride(1) == 1 and frames.shape[0] == B
+    assert tok_lp.shape == frames.shape and tok_dur.shape == frames.shape and frames.stride(0) == tok_lp.stride(0) == tok_dur.stride(0)
+    assert score.dtype is torch.float64 and score.is_contiguous() and score.shape[0] == B
+    check(lib().ttmi_tdt_advance(_p(dec), _p(lp), c_int(B), c_int(n), c_int(blank), dur, D, c_int(n_hist), _p(hist), c_long(hist.stride(0)),
+                                 _p(t), _p(T_len), _p(need), _p(done), _p(count), _p(flags), _p(frames), _p(tok_lp), _p(tok_dur),
+                                 c_long(frames.stride(0)), _p(score), _stream()), "ttmi_tdt_advance")
+
+
+class TDTLattice:
+    """The token-and-duration lattice as a record that quacks like `Lattice` for _LatticeLossFn (warprnnt_pytorch) and _JointLossFn
+    (tt.model): .workspace / .loss_fwd / .loss_bwd with their signatures, and the facts callers branch on.  It is NOT in LATTICES: it is no
+    topology of the same logits (its rows are V + D wide) and carries its durations.  Alignment and emission statistics are not built."""
+    name, takes_fastemit, has_exp_forms, label_takes_frame = "tdt", False, False, True
+
+    def __init__(self, durations):
+        self.durations = check_durations(durations)
+
+    def fastemit_kw(self, fastemit_lambda):
+        return {}
+
+    def workspace(self, B, T, U1, device):
+        return tdt_workspace(B, T, U1, len(self.durations), device)
+
+    def loss_fwd(self, logits, labels, act_lens, label_lens, blank, workspace):
+        return tdt_loss_fwd(logits, labels, act_lens, label_lens, blank, self.durations, workspace)
+
+    def loss_bwd(self, logits, labels, act_lens, label_lens, blank, workspace, grad_out, grad_out_stride, scale, inplace=False):
+        return tdt_loss_bwd(logits, labels, act_lens, label_lens, blank, self.durations, workspace, grad_out, grad_out_stride, scale, inplace)
+
+    def align(self, *args, **kwargs):
+        raise ValueError("TDT: forced alignment is not built on the token-and-duration lattice")
+
+    def emit_stats(self, *args, **kwargs):
+        raise ValueError("TDT: emission statistics are not built on the token-and-duration lattice")
+
+
 # ----------------------------------------------------------------------------- distillation on collapsed lattice posteriors (csrc/distill.hip)
 def kd_workspace(B, T, U1, device):
     n = _sized("ttmi_kd_workspace_bytes", c_int(B), c_int(T), c_int(U1))

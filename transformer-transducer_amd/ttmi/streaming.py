@@ -43,6 +43,9 @@ class StreamingRecognizer:
     def __init__(self, model, left_context=None, right_context=None, n_layer=None, n_mels=128, max_history=40, block=64,
                  sample_rate=16000, details=False, beam_width=None, nbest=None, context=None, lm=None, lm_weight=0.0, ilm_weight=0.0,
                  length_bonus=0.0):
+        if getattr(model, "tdt_durations", None) is not None:
+            from .tdt import not_built
+            raise not_built("StreamingRecognizer")
         if beam_width is None:
             if context is not None or lm is not None or nbest is not None or any(float(v) != 0.0 for v in (lm_weight, ilm_weight, length_bonus)):
                 raise ValueError("StreamingRecognizer: nbest, context, lm, lm_weight, ilm_weight and length_bonus need beam_width (the greedy "
